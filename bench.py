@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark of the calibrate + sigma-clip-stack hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--parallelism nshard|rowshard]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--parallelism nshard|rowshard] [--full]
+                    [--dump-outputs DIR]
 
 A step = one pass of the hot path over one batch of synthetic frames already resident in HBM: fused
 bias/dark/flat calibration + 3-sigma (maxiters 5, median-centred) clipped mean along N.
@@ -24,8 +25,15 @@ parent touches the GPU) unless it already runs under a launcher (torchrun sets W
 RCCL (torch.distributed backend "nccl") on 127.0.0.1.  The run fails (non-zero exit) if the process group's world size
 differs from --gpus.
 
-Prints ONE JSON line (rank 0) with the whole-job Mpixels/s, the HBM roofline of the dominant kernel (measured live
-with HIP events on the launch stream) and the CPU baselines timed beside it (the C/OpenMP oracle and the NumPy path).
+Prints ONE JSON line (rank 0) with the whole-job Mpixels/s and the HBM roofline of the dominant kernel (measured live
+with HIP events on the launch stream).  A plain run sets up, warms up, times the --steps steps and prints that line; --full
+adds the measurements that take runs of their own: the CPU baselines (the C/OpenMP oracle and the NumPy path), the
+device-to-device copy rate beside the roofline, and for an N-sharded step the stripe kernels alone ("compute_ms"), the
+exact kernel ("exact_ms") and the row-shard form of the same job ("rowshard").
+
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float32; rank 0's result): an output larger
+than DUMP_MAX_BYTES is a fixed, seeded sample of its pixels (the same pixels for the same shape), so that two builds of
+the project can be compared output for output on the same synthetic inputs.
 """
 import argparse
 import json
@@ -40,6 +48,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); 6.3 TB/s is the achievable copy rate
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: all files of one dump together
 
 
 def parse(argv=None):
@@ -80,7 +89,11 @@ def parse(argv=None):
     ap.add_argument('--hier-shards', type=int, default=8, help='--scaling strong: the job is this many shards of '
                                                                'total-frames / shards frames, whatever --gpus is')
     ap.add_argument('--exact-moments', action='store_true', help='APGPU_STACK_EXACT_MOMENTS: float64 clip only (no float32 fast path)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also run the measurements beside the headline figure: CPU baselines, the '
+                    'device copy rate, and (N-sharded steps) compute_ms / exact_ms / the row-shard leg')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last one returned as '
+                    'DIR/<name>.npy (float32; a fixed seeded sample of the pixels when larger than %d MiB in all)' % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines')
     ap.add_argument('--force-collective', action='store_true', help='run the striped all-reduce path even with one rank (testing)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0, help='target CPU time of each cpu_baseline leg')
     ap.add_argument('--master-port', type=int, default=0, help='rendezvous port of the built-in launcher (0 = pick a free one)')
@@ -203,6 +216,32 @@ def cpu_baseline(frames, masters, nflat, e, seconds):
     except Exception as exc:                                  # the baseline is a report, never a reason to lose the bench line
         out['numpy'] = dict(error=repr(exc))
     return out
+
+
+def dump_outputs(out, dirname, name='mean'):
+    """Writes the arrays a caller of the timed step receives as dirname/<name>.npy (float32, float64 kept as it is).  When
+    they exceed DUMP_MAX_BYTES together, each is a sample of its elements in flat order, the same elements for the same
+    shape (numpy Generator seeded with 20240 + the element count), so that dumps of two builds line up element for element."""
+    import numpy as np
+    import torch
+    if isinstance(out, torch.Tensor):
+        named = {name: out}
+    elif isinstance(out, dict):
+        named = {k: v for k, v in out.items() if isinstance(v, torch.Tensor)}
+    else:
+        named = {'out%d' % i: v for i, v in enumerate(out) if isinstance(v, torch.Tensor)}
+    arrays = {}
+    for k, v in named.items():
+        a = v.detach().cpu().numpy()
+        arrays[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = np.random.default_rng(20240 + a.size).random(a.size) < 0.95 * DUMP_MAX_BYTES / total
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(dirname, k + '.npy'), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def selftest_cpu(args, world, rank):
@@ -422,6 +461,8 @@ def main(argv=None):
         dist.all_gather(allt, mine)
         per_rank_ms = [1e3 * float(v.item()) / args.steps for v in allt]
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs, name='median' if wl == 'c4' else 'mean')
     # what the stack's fast kernels left to the redo pass over the timed steps (counters in the workspace, read after the clock)
     redo = ops.stack_redo_stats()
     job_pixels = float(N) * P                                  # input frame pixels of ALL ranks (ragged blocks: summed, not
@@ -458,7 +499,7 @@ def main(argv=None):
         exchange_ms = float(t.item())
 
     extra = {}
-    if wl == 'c2' and not rowshard and not single_launch:
+    if args.full and wl == 'c2' and not rowshard and not single_launch:
         # (0) what one SCALE run needs to diagnose itself: the stripes' moment kernels alone (no collective: `compute_ms`, max over
         # ranks), the collectives' time on the communication stream (`exchange_ms` above) and how much of it hid behind the
         # kernels: overlap = (compute + exchange - step) / exchange, 1 = fully hidden, 0 = fully exposed
@@ -559,7 +600,7 @@ def main(argv=None):
     # the box's achievable streaming rate beside the nominal peak: device-to-device copy of
     # 1 GiB, read + write bytes over the best of 10 runs
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -629,7 +670,7 @@ def main(argv=None):
             if hier_chunk:
                 line['hier_shards'] = args.hier_shards
         line.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.dtype == 'f32' and wl == 'c2':
                 line['cpu_baseline'] = cpu_baseline(frames, masters, nflat, e, args.cpu_seconds)
             else:

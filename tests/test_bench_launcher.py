@@ -45,3 +45,20 @@ def test_single_rank_selftest():
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads(r.stdout.decode().strip())
     assert d['n_gpus'] == 1 and d['rccl_world_size'] == 1
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: small outputs are written whole (float64 kept), a larger one as the same seeded sample every time."""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.parse(['--steps', '7']).steps == 7 and not bench.parse([]).full and bench.parse([]).dump_outputs is None
+    small = {'mean': torch.arange(12, dtype=torch.float32).reshape(3, 4), 'std': torch.ones(3, 4, dtype=torch.float64)}
+    assert bench.dump_outputs(small, str(tmp_path / 's')) == ['mean', 'std']
+    m, s = np.load(tmp_path / 's' / 'mean.npy'), np.load(tmp_path / 's' / 'std.npy')
+    assert m.dtype == np.float32 and m.shape == (3, 4) and np.array_equal(m, small['mean'].numpy()) and s.dtype == np.float64
+    big = torch.from_numpy(np.random.default_rng(3).random((4096, 4096), dtype=np.float32))
+    for k in ('a', 'b'):
+        bench.dump_outputs(big, str(tmp_path / k))
+    a, b = np.load(tmp_path / 'a' / 'mean.npy'), np.load(tmp_path / 'b' / 'mean.npy')
+    assert a.dtype == np.float32 and 0 < a.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(a, b)

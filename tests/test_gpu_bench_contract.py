@@ -22,7 +22,7 @@ def _run(*extra):
 
 
 def test_default_workload_line():
-    d = _run('--frames', '16')
+    d = _run('--frames', '16', '--full')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in d, k
@@ -37,6 +37,21 @@ def test_default_workload_line():
     assert cb['kind'] == 'port' and cb['cores'] >= 1 and cb['value'] > 0 and 'sample' in cb
     assert cb['numpy']['single_process']['value'] > 0 and cb['numpy']['single_process']['cores'] == 1 and cb['numpy']['cpu']
     assert abs(d['value'] - 16 * 256 * 512 / 1e6 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+
+
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figure only (no CPU baseline, no copy-rate run); --dump-outputs writes the
+    last timed step's mean, and the same arguments give the same inputs, hence the same outputs, from run to run."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = _run('--frames', '16', '--dump-outputs', str(tmp_path / ('d%d' % k)))
+        assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['value'] > 0 and d['metric'] and d['dtype'] == 'f32'
+        assert 'cpu_baseline' not in d and d['roofline']['measured_copy_GBps'] is None
+        assert sorted(os.listdir(tmp_path / ('d%d' % k))) == ['mean.npy']
+        runs.append(np.load(tmp_path / ('d%d' % k) / 'mean.npy'))
+    assert runs[0].dtype == np.float32 and runs[0].shape == (256, 512) and np.isfinite(runs[0]).all()
+    np.testing.assert_array_equal(runs[0], runs[1])
 
 
 def test_other_workloads_run():
@@ -65,7 +80,7 @@ def test_multi_rank_paths_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'MASTER_ADDR')}
     env['APGPU_BENCH_ONE_GPU_TEST'] = '1'
     base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--height', '128',
-            '--width', '512', '--frames', '16', '--no-cpu-baseline']
+            '--width', '512', '--frames', '16', '--no-cpu-baseline', '--full']
     for extra in ([], ['--exchange', 'f32'], ['--exchange', 'f64'], ['--scaling', 'strong', '--total-frames', '64', '--hier-shards', '4'],
                   ['--parallelism', 'rowshard'], ['--scaling', 'strong', '--total-frames', '64', '--parallelism', 'rowshard']):
         r = subprocess.run(base + extra, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)

@@ -302,7 +302,7 @@ def _g11_case(g, ci):
 def test_g11_calibrate_float64(golden_dir):
     """float64 masters / raw frames: NumPy's per-operation promotion, float64 flat normalisation and bad-pixel repair."""
     from oracle import apref
-    g = load(golden_dir, 'g11_calibrate_f64.npz')
+    g = {**load(golden_dir, 'g11_calibrate_f64.npz'), **load(golden_dir, 'g11_calibrate_f64_cases.npz')}
     for j in range(int(g['nsums'])):
         a = g[f's{j}_a']
         assert apref.lib().apref_pairwise_sum_f64(a.ctypes.data_as(__import__('ctypes').c_void_p), __import__('ctypes').c_long(a.size)) \

@@ -10,6 +10,11 @@ def load_golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+def load_g11():
+    """G11 is stored as two archives (each under the size limit of a committed file); one mapping of all its arrays."""
+    return {**load_golden('g11_calibrate_f64.npz'), **load_golden('g11_calibrate_f64_cases.npz')}
+
+
 def meta(g, key):
     return json.loads(str(g[key]))
 

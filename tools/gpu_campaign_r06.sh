@@ -24,5 +24,5 @@ head -40 $O/bench_kernels.txt | cut -c1-120
 cat $O/bench_big.txt | cut -c1-200
 cat $O/bench_a6.txt | cut -c1-160
 cat $O/bench_fused.txt
-python bench.py --force-collective --no-cpu-baseline --steps 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('force-collective (one rank):', d['ms_per_step'], 'ms', d.get('exchange'), 'compute_ms', d.get('compute_ms'), 'overlap', d.get('exchange_overlap_frac'))"
+python bench.py --full --force-collective --no-cpu-baseline --steps 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('force-collective (one rank):', d['ms_per_step'], 'ms', d.get('exchange'), 'compute_ms', d.get('compute_ms'), 'overlap', d.get('exchange_overlap_frac'))"
 python bench.py --force-collective --no-gather --no-cpu-baseline --steps 10 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('force-collective, no gather (one rank):', d['ms_per_step'], 'ms', d.get('exchange_bytes_on_wire'))"
