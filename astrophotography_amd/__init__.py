@@ -20,6 +20,7 @@ _LAZY = {
     'ApCalcReadNoise': ('.core.ApCalcReadNoise', 'ApCalcReadNoise'),
     'ApMeasureBackground': ('.core.ApMeasureBackground', 'ApMeasureBackground'),
     'ApFixCosmicRays': ('.core.ApFixCosmicRays', 'ApFixCosmicRays'),
+    'ApAutoBadcols': ('.core.ApAutoBadcols', 'ApAutoBadcols'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

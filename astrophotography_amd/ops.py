@@ -544,6 +544,90 @@ def sigclip_global(data, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters
     return stats
 
 
+def _median_dtype(x):
+    """F5 inputs: float32 stays float32; float64 and integer tensors -> float64 (numpy takes the median of integers in
+    float64; every integer converts monotonically, so widening first selects the same element)."""
+    if x.dtype == torch.float32:
+        return x.contiguous(), APGPU_F32
+    if x.dtype == torch.uint16:
+        return x.contiguous(), APGPU_U16                # widened to float64 inside the kernel
+    if x.dtype not in (torch.float64, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise TypeError('axis medians take float32, float64 or integer data, got %s' % x.dtype)
+    return x.to(torch.float64).contiguous(), APGPU_F64
+
+
+def axis_nanmedian(x, axis):
+    """F5 np.nanmedian(x, axis) of an image [H, W] or of every frame of a slab [N, H, W] (ApAutoBadcols.py:196, :200).
+
+    axis 0 (or -2): per column -> [W] / [N, W]; axis 1 (or -1): per row -> [H] / [N, H].  float32 data gives float32
+    medians, float64 and integer data float64 medians, bit-exact with numpy 1.26 (both of its nanmedian paths)."""
+    _need_cuda(x)
+    if x.dim() not in (2, 3):
+        raise ValueError('axis_nanmedian takes [H, W] or [N, H, W], got shape %s' % (tuple(x.shape),))
+    if axis not in (0, 1, -1, -2):
+        raise ValueError('axis must be 0 or 1 (an axis of one image), got %r' % (axis,))
+    axis = axis % 2
+    single = x.dim() == 2
+    x3 = x.unsqueeze(0) if single else x
+    N, H, W = x3.shape
+    if N == 0 or H == 0 or W == 0:
+        raise ValueError('axis_nanmedian: empty input of shape %s' % (tuple(x.shape),))
+    d, dt = _median_dtype(x3)
+    out = torch.empty((N, W if axis == 0 else H), dtype=torch.float32 if dt == APGPU_F32 else torch.float64, device=d.device)
+    check(_lib.load().apgpu_axis_nanmedian(_ptr(d), dt, N, H, W, axis, _ptr(out), _stream()))
+    return out[0] if single else out
+
+
+def sliding_clipped_stats(v, window_len, sigma=3.0, maxiters=5, nsigma=5.0):
+    """F5 ApAutoBadcols._sliding_stats_1d (ApAutoBadcols.py:143-167) and the flag of _process (:225-227) for one line
+    [L] or a batch of lines [B, L] (float32 or float64; numpy's statistics in that dtype).
+
+    maxiters None = until convergence.  Returns dict(mean, std, nsig: float64, flag: uint8), each shaped like v."""
+    _need_cuda(v)
+    if v.dim() not in (1, 2) or v.numel() == 0:
+        raise ValueError('sliding_clipped_stats takes a non-empty [L] or [B, L] tensor, got shape %s' % (tuple(v.shape),))
+    window_len = int(window_len)
+    if window_len < 1:
+        raise ValueError('window_len must be >= 1, got %d' % window_len)
+    if v.dtype == torch.float32:
+        dt = APGPU_F32
+    elif v.dtype == torch.float64:
+        dt = APGPU_F64
+    else:
+        raise TypeError('sliding_clipped_stats takes float32 or float64 values, got %s' % v.dtype)
+    v2 = v.reshape(1, -1) if v.dim() == 1 else v
+    v2 = v2.contiguous()
+    B, L = v2.shape
+    lib = _lib.load()
+    ws_bytes = lib.apgpu_sliding_clipped_stats_ws_bytes(dt, B, L, window_len)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device)
+    mean = torch.empty((B, L), dtype=torch.float64, device=v.device)
+    std = torch.empty_like(mean)
+    nsig = torch.empty_like(mean)
+    flag = torch.empty((B, L), dtype=torch.uint8, device=v.device)
+    check(lib.apgpu_sliding_clipped_stats(_ptr(v2), dt, B, L, window_len, float(sigma), -1 if maxiters is None else int(maxiters),
+                                          float(nsigma), _ptr(mean), _ptr(std), _ptr(nsig), _ptr(flag), _ptr(ws), ws_bytes,
+                                          _stream()))
+    r = dict(mean=mean, std=std, nsig=nsig, flag=flag)
+    return {k: t.reshape(v.shape) for k, t in r.items()}
+
+
+def auto_badcols(data, nsigma=5.0, window_len=11):
+    """F5 ApAutoBadcols.process (ApAutoBadcols.py:180-258) on the device, for an image [H, W] or a slab [N, H, W]:
+    column and row medians, their sliding clipped statistics and the bad flags, launched back to back on the current
+    stream without a host synchronisation.
+
+    Returns {'cols': dict(median, mean, std, nsig, flag), 'rows': ...}, device tensors shaped [W] / [H] (or [N, W] /
+    [N, H]); indices with flag 1 are the reference's bad columns / rows (0-based)."""
+    out = {}
+    for tag, axis in (('cols', 0), ('rows', 1)):
+        med = axis_nanmedian(data, axis)
+        r = sliding_clipped_stats(med, window_len, nsigma=nsigma)
+        r['median'] = med
+        out[tag] = r
+    return out
+
+
 def image_difference(a, b, bad1=None, bad2=None):
     """F2 ApImageDifference (ap_calc_read_noise.py:122): float64(a) - float64(b), NaN where bad1|bad2."""
     _need_cuda(a, b, bad1, bad2)

@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form) */
+#define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form);
+                                       additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes) */
 
 /* error codes */
 #define APGPU_OK            0
@@ -276,6 +277,32 @@ int apgpu_sigclip_global_f32(const float *data, int64_t n_pixels, double sigma_l
 size_t apgpu_sigclip_global_f64_ws_bytes(int64_t n_pixels);
 int apgpu_sigclip_global_f64(const double *data, int64_t n_pixels, double sigma_lower, double sigma_upper,
                              int maxiters, double *stats_out, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F5  ApAutoBadcols.process (core/ApAutoBadcols.py:180-258), the bad column / row finder of
+ *     scripts/ap_auto_badcol.py:76-116.  dtype: APGPU_F32 or APGPU_F64; numpy takes the median of integers in
+ *     float64, so uint16 images are APGPU_U16 below and other integer images are widened exactly by the caller.
+ *     apgpu_axis_nanmedian: np.nanmedian(data, axis) of every frame of a slab [N][H][W] (:196, :200); axis 0 ->
+ *       out [N][W] (per column), axis 1 -> out [N][H] (per row), in the data's dtype (APGPU_U16: float64 out, the
+ *       pixels widened as they are read).  Exact order statistic of the non-NaN values; numpy 1.26's two paths are
+ *       both reproduced: lines shorter than 600 go through np.ma.median (the middle value of an odd count is
+ *       T(x + x) / 2), longer ones through np.median (the value itself); an even count gives T(a + b) / 2; an
+ *       all-NaN line gives NaN.  n_frames <= 65535.
+ *     apgpu_sliding_clipped_stats: _sliding_stats_1d (:143-167) and the flag of _process (:225-227) for n_lines
+ *       lines of `length` values each: for every index i the window values[max(0, i - hw) : min(L, i + hw + 1)],
+ *       hw = (window_len - 1) / 2, is clipped exactly as by the A3 entry points (astropy's noaxis clip,
+ *       sigma_lower = sigma_upper = sigma; maxiters < 0 = until convergence) and
+ *         mean[i], std[i]  = the clipped mean and std (float64 holding values of the dtype),
+ *         nsig[i]          = |float64(values[i]) - mean[i]| / std[i]   (float64; std == 0 gives inf or NaN),
+ *         flag[i]          = nsig[i] >= nsigma                         (uint8 0 / 1; NaN is not bad).
+ *       window_len >= 1 (a window longer than the line is cut at both ends); ws >= the _ws_bytes value.
+ * ------------------------------------------------------------------------------------------- */
+int apgpu_axis_nanmedian(const void *data, int dtype, int64_t n_frames, int64_t height, int64_t width, int axis, void *out,
+                         void *stream);
+size_t apgpu_sliding_clipped_stats_ws_bytes(int dtype, int64_t n_lines, int64_t length, int64_t window_len);
+int apgpu_sliding_clipped_stats(const void *values, int dtype, int64_t n_lines, int64_t length, int64_t window_len, double sigma,
+                                int maxiters, double nsigma, double *mean, double *std, double *nsig, uint8_t *flag, void *ws,
+                                size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * F2  ApImageDifference (scripts/ap_calc_read_noise.py:122): out = float64(a) - float64(b) where neither
