@@ -245,9 +245,13 @@ __global__ __launch_bounds__(256, 3) void resample_clip_kernel(const StackParams
                 for (int j = 1; j <= T; j++) nonfin += (c[NP - j] == __builtin_inff()) ? 1 : 0;
                 good = good && nonfin < T;
                 if (wave_any(good)) finish_fast_column<NP, T, false>(c, good, p, 0, nonfin);
-                if (inside && !good) {                         // an unsure lane: the exact clip, here
+                if (inside && !good) {
+                    // an unsure lane: complete the sort, then the exact clip, here.  Not reduce_and_store(pruned = true):
+                    // that flag promises a full column in every lane of the wave, and this is a divergent branch whose
+                    // columns may hold +inf sentinels.
+                    sort_column<NP>(c);
                     const StackParams q = read_params(late_params());
-                    reduce_and_store<NP, NP>(q, c, n, p, true, false);
+                    reduce_and_store<NP, NP>(q, c, n, p, false, false);
                 }
                 continue;
             }

@@ -543,7 +543,9 @@ __global__ __launch_bounds__(256, APGPU_CHUNKS_MINBLOCKS) void stack_chunks_kern
     S = (Stot + f.Slo) + f.Shi;
     Q = (Qtot + f.Qlo) + f.Qhi;
     const int cnt = N - f.ta - f.tb;
-    f.unsure = f.unsure || !(16.f * Q <= (float)cnt * (c0 * c0));          // mean-accuracy guard, see clip_fast32
+    // mean-accuracy guard, see clip_fast32.  (The host model of the mean, tools/fast32_model.py, does not describe these sums -
+    // chunk partials in longer chains: no worst-case search has covered this path, the guard alone stands here.)
+    f.unsure = f.unsure || !((float)APGPU_FAST32_MEAN_GUARD * Q <= (float)cnt * (c0 * c0));
     // Round 6 - the median and std planes of the FINAL survivors (np.nanmedian / np.nanstd of what the clip kept) for 129 .. 512
     // frames, which used to send the whole stack to the LDS-resident exact kernel (25 ms for 256 frames, 120 for 512):
     //   median: the middle pair of the final range [ta, N - tb) from the merged window, under the same two conditions as the
@@ -1061,7 +1063,7 @@ __global__ __launch_bounds__(256) void stack_mad_sums_kernel(const StackParams p
     if (prm.mean64) prm.mean64[p] = mean;
     if (prm.std64) {
         const double var = (Q - S * S / nn) / nn;
-        prm.std64[p] = sqrt(var > 0.0 ? var : 0.0);
+        prm.std64[p] = n > 0 ? sqrt(var > 0.0 ? var : 0.0) : __builtin_nan("");   // every value rejected: NaN, as the oracle
     }
 }
 

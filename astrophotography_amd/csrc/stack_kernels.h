@@ -480,6 +480,22 @@ __device__ __forceinline__ void finish_fast_column(const float (&v)[NP], bool &g
     float cf, Sf, Qf;
     const bool done = clip_fast32<NP, T, CALIB ? 1 : 2, PLO, PHI>(v, (float)kp->sl2, (float)kp->su2, kp->maxiters, a, b, cf, Sf, Qf, plo, phi);
     good = good && done;
+    if constexpr (NP > 96) {
+        // More than 96 slots: the mean guard rms(d) <= |c| / 4 alone is not enough.  The rounding error of S grows with the
+        // length of its chains, and the worst-case search of the host model (tools/fast32_search.py) finds 128-frame columns
+        // with rms(d) / |c| near 1/4 whose cf + ms32 lies 1.1 ulp from the exact mean - rounded, 2 ulp.  Up to 96 slots it
+        // stays below 1 ulp (tails of 4: 0.94 at 64, 0.86 at 96; tails of 8: 0.61, 0.84).  So here a lane with rms(d) > |c| / 8 (where the error can pass 0.6 ulp)
+        // finishes only when the unrounded mean lies within a quarter ulp of its float32 - the Fast2Sum residual of cf + ms32,
+        // |cf| >= |ms32| under the guard; the others go to the list.  (The benchmark's 64-slot kernels do not compile this.)
+        const float nf32 = (float)(b - a);
+        const float y = __builtin_amdgcn_rcpf(nf32);
+        const float q0 = Sf * y;
+        const float ms32 = __builtin_fmaf(__builtin_fmaf(-nf32, q0, Sf), y, q0);
+        const float mean = cf + ms32;
+        const float res = ms32 - (mean - cf);
+        const bool wide = !(64.f * Qf <= nf32 * (cf * cf));
+        good = good && !(wide && !(__builtin_fabsf(res) <= __builtin_fabsf(mean) * 0x1p-26f));
+    }
     if (good) {
         LateParams *const ko = late_params();
         const int cnt = b - a;

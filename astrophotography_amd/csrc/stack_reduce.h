@@ -292,6 +292,12 @@ __device__ __forceinline__ void store_moments(void *out, int f64_layout, int64_t
 #ifndef APGPU_FAST32_RHO
 #define APGPU_FAST32_RHO 0x1p-15f
 #endif
+// the mean-accuracy guard G Q <= n c^2, i.e. rms(d) <= |c| / sqrt(G) (see the end of clip_fast32; stack_chunks.hip has the same
+// guard): 16 in release builds.  A variant build with the old, looser guard (4: |c| / 2) is what the fast path's mean tests
+// must catch (tests/test_gpu_fast32_mean.py, tools/fast32_search.py).
+#ifndef APGPU_FAST32_MEAN_GUARD
+#define APGPU_FAST32_MEAN_GUARD 16
+#endif
 
 struct Fast32 {
     float m1, m2;                       // the middle pair of the current range (its median is their mean)
@@ -520,7 +526,7 @@ __device__ __forceinline__ bool clip_fast32(const float (&v)[NP], float sl2f, fl
     // sent 1.2 % of C2's and 19 % of C5's pixels to the redo pass, 0.89 -> 1.13 and 5.1 -> 6.0 ms)
     S = (Sc + f.Slo) + f.Shi;
     Q = (Qc + f.Qlo) + f.Qhi;
-    f.unsure = f.unsure || !(16.f * Q <= (float)(f.b - f.a) * (cf * cf));
+    f.unsure = f.unsure || !((float)APGPU_FAST32_MEAN_GUARD * Q <= (float)(f.b - f.a) * (cf * cf));
     a_out = f.a;
     b_out = f.b;
     cf_out = cf;

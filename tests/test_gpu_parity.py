@@ -794,6 +794,35 @@ def test_fast32_path_guards_on_adversarial_columns(ops, apref):
                 assert_ulp(host(plus['mean']), ref['mean'].astype(np.float32), 1, what + ' planes: mean')
                 assert_ulp(host(plus['median']), ref['median'].astype(np.float32), 1, what + ' planes: median')
                 assert_ulp(host(plus['std']), ref['std'].astype(np.float32), 2, what + ' planes: std')
+    # level / spread ratios across the band of the mean-accuracy guard (rms(d) <= |c| / 4 since round 6; the old |c| / 2 let
+    # 2-ulp means through between 1/8 and 1/2): both signs, means just below a power of two, Gaussian / exponential / two-level
+    rng = np.random.default_rng(2026)
+    ratios = np.array([0.15, 0.2, 0.24, 0.26, 0.3, 0.45])
+    for N in (13, 16, 24, 30, 48, 61, 64, 96, 128, 160, 256, 300):
+        ratio = ratios[rng.integers(0, len(ratios), (H, W))]
+        level = np.where(rng.random((H, W)) < 0.5, -1.0, 1.0) * np.ldexp(1.0 - rng.uniform(0, 2.0 ** -8, (H, W)), rng.integers(-4, 12, (H, W)))
+        kind = rng.integers(0, 3, (H, W))
+        z = np.where(kind == 0, rng.normal(size=(N, H, W)),
+                     np.where(kind == 1, rng.exponential(size=(N, H, W)) - np.log(2.0), (rng.random((N, H, W)) < 0.3) * 2.0 - 0.6))
+        z *= np.where(rng.random((H, W)) < 0.5, -1.0, 1.0)
+        cube = (level * (1.0 + ratio * z)).astype(np.float32)
+        d = dev(cube, ops)
+        # (sigma 2.7 and 3: no two-level column of up to 300 values sits exactly on a bound, k (N - k) sigma^2 = N^2)
+        for sigma, maxiters in ((3.0, 5), (2.7, None)):
+            ref = apref.stack_sigclip(cube, sigma=sigma, maxiters=maxiters)
+            what = f'ratio band N={N} sigma={sigma} maxiters={maxiters}'
+            fast = ops.stack_sigclip(d, sigma=sigma, maxiters=maxiters, outputs=('mean', 'count'))
+            exact = ops.stack_sigclip(d, sigma=sigma, maxiters=maxiters, outputs=('mean', 'count'), exact=True)
+            assert np.array_equal(host(fast['count']), ref['count']), what
+            assert np.array_equal(host(exact['count']), ref['count']), what
+            assert_ulp(host(exact['mean']), ref['mean'].astype(np.float32), 1, what + ' float64 path')
+            assert_ulp(host(fast['mean']), ref['mean'].astype(np.float32), 1, what + ' float32 fast path')
+            if N <= 96:
+                plus = ops.stack_sigclip(d, sigma=sigma, maxiters=maxiters, outputs=('mean', 'median', 'std', 'count'))
+                assert np.array_equal(host(plus['count']), ref['count']), what
+                assert_ulp(host(plus['mean']), ref['mean'].astype(np.float32), 1, what + ' planes: mean')
+                assert_ulp(host(plus['median']), ref['median'].astype(np.float32), 1, what + ' planes: median')
+                assert_ulp(host(plus['std']), ref['std'].astype(np.float32), 2, what + ' planes: std')
 
 
 def test_unfused_stacks_with_nonfinite_values(ops, apref):

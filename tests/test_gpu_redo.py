@@ -507,3 +507,32 @@ def test_calibrated_median_129_to_512_frames(ops, apref, N, dtype):
         rows = ops.stack_median(d[:, 2:9], calib={k: (v[2:9] if k in ('bias', 'dark', 'nflat') else v) for k, v in calib.items()},
                                 pixmask=dev(pm[2:9], ops) if use_pm else None)
         np.testing.assert_array_equal(rows.cpu().numpy(), med[2:9].cpu().numpy(), err_msg='stripe ' + what)
+
+
+@pytest.mark.parametrize('N,dtype', [(130, np.float32), (256, np.float32), (300, np.uint16), (512, np.float32)])
+def test_ccdproc_configuration_129_to_512_frames_rejecting_everything(ops, apref, N, dtype):
+    """mad_std with sigma = 0.5 on two-level columns of an even length: the bounds median +- 0.5 * 1.4826 MAD lie inside both
+    levels, so the chunked sums pass rejects every value with certainty.  Nothing survives: count 0, mean and std NaN, as in the
+    oracle (and in the exact kernel)."""
+    H, W = 4, 96
+    rng = np.random.default_rng(1900 + N)
+    lo = np.rint(rng.uniform(200.0, 900.0, (H, W)))
+    hi = lo + np.rint(rng.uniform(3.0, 40.0, (H, W)))
+    two = np.zeros((N, H, W), bool)
+    two[: N // 2] = True
+    two = rng.permuted(two, axis=0)
+    cube = np.where(two, hi[None], lo[None])
+    cube[:, 3, :] = rng.normal(500.0, 10.0, (N, W))                   # ordinary columns next to them
+    cube = np.clip(np.rint(cube), 0, 65535).astype(np.uint16) if dtype == np.uint16 else cube.astype(np.float32)
+    d = dev(cube, ops)
+    for form, flag in (('legacy', False), ('astropy', True)):
+        ref = apref.combine_ccdproc(cube.astype(np.float32) if dtype == np.uint16 else cube, low=0.5, high=0.5, form=form)
+        assert (ref['count'][:3] == 0).all() and np.isnan(ref['std'][:3]).all() and np.isnan(ref['mean'][:3]).all()
+        for kw in (dict(), dict(exact=True)):
+            what = '%d frames %s %s %s' % (N, np.dtype(dtype).name, form, kw)
+            r = ops.stack_sigclip(d, sigma=0.5, maxiters=1, cenfunc='median', stdfunc='mad_std', outputs=('mean', 'count', 'mean_f64', 'std_f64'),
+                                  nonfinite_unclipped=flag, **kw)
+            assert np.array_equal(r['count'].cpu().numpy(), ref['count']), what
+            np.testing.assert_allclose(r['mean_f64'].cpu().numpy(), ref['mean'], rtol=4e-16, atol=0, equal_nan=True, err_msg=what)
+            np.testing.assert_allclose(r['std_f64'].cpu().numpy(), ref['std'], rtol=1e-12, atol=1e-12, equal_nan=True, err_msg=what)
+            assert_ulp(r['mean'].cpu().numpy(), ref['mean'].astype(np.float32), 1, what)

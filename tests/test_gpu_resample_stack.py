@@ -75,6 +75,32 @@ def test_fused_matches_oracle_composition(ops, apref, N):
     assert cnt.max() <= N and cnt[100, 160] >= N - 3
 
 
+@pytest.mark.parametrize('N', [16, 15, 14, 13])
+def test_fused_v1_kernel_more_than_1024_phases(ops, apref, N):
+    """Weight tables of more than 1024 phases take the first form of the kernel (resample_clip_kernel, v1): a pixel mask, frame
+    borders (shifts of several pixels: columns with +inf sentinels) and outliers, so that some lanes of a wavefront leave the
+    fast path for the exact clip while the others finish.  Against the oracle's composition with the same table."""
+    import torch
+    rng = np.random.default_rng(640 + N)
+    frames = _frames(rng, N, (150, 210))
+    frames[2, 60:70, 80:90] += 3000.0                             # a block of outliers in one frame
+    A = _affines(rng, N, max_rot_deg=0.5, max_shift=6.0)
+    mask = (rng.random((150, 210)) < 4e-3).astype(np.uint8)
+    mask[40:44, 100:130] = 1
+    fr = torch.from_numpy(frames).cuda()
+    mk = torch.from_numpy(mask).cuda()
+    for sigma, maxiters in ((3.0, 5), (2.0, None)):
+        r = ops.resample_stack_sigclip(fr, A, mask=mk, n_phases=2048, sigma=sigma, maxiters=maxiters, outputs=('mean', 'count'))
+        torch.cuda.synchronize()
+        res_ref, _ = apref.resample_affine(frames, A, mask=mask, n_phases=2048)
+        ref = apref.stack_sigclip(res_ref, sigma=sigma, maxiters=maxiters)
+        cnt = r['count'].cpu().numpy()
+        what = 'N=%d sigma=%g' % (N, sigma)
+        assert np.array_equal(cnt, ref['count']), '%s: survivor counts differ at %s' % (what, np.argwhere(cnt != ref['count'])[:5].tolist())
+        assert_ulp(r['mean'].cpu().numpy(), ref['mean'].astype(np.float32), 1, what)
+        assert (cnt < N).any() and (cnt == N).any(), what
+
+
 def test_fused_with_bad_pixel_mask_and_nan_inputs(ops, apref):
     rng = np.random.default_rng(611)
     N = 16
