@@ -327,8 +327,16 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
             const double total = block_sum<NT>(sum, scratch);
             if (n_unmasked < 0) n_unmasked = n;
             if (n == 0) {
-                med = sd = __builtin_nan("");
-                break;
+                if (final_pass || pass == 0) {
+                    med = sd = __builtin_nan("");
+                    break;
+                }
+                // a pass before maxiters removed everything: astropy's next pass divides 0 by 0, its bounds are NaN, no comparison
+                // with them masks anything - every unmasked finite value of the box survives (golden group G15 holds such boxes)
+                lo_last = -3.4028234663852886e38f;
+                hi_last = 3.4028234663852886e38f;
+                n_prev = -2;
+                continue;
             }
             if (!final_pass && n == n_prev) {               // the last bounds removed nothing: converged, evaluate the survivors
                 n_prev = -2;
@@ -404,8 +412,16 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
             n = (int)block_sum<NT>(cnt, scratch);
             const double S1 = block_sum<NT>(s1, scratch), S2 = block_sum<NT>(s2, scratch);
             if (n == 0) {
-                med = sd = __builtin_nan("");
-                break;
+                if (final_pass || pass == 0) {
+                    med = sd = __builtin_nan("");
+                    break;
+                }
+                // a pass before maxiters removed everything: astropy's next pass divides 0 by 0, its bounds are NaN, no comparison
+                // with them masks anything - every unmasked finite value of the box survives (golden group G15 holds such boxes)
+                lo_last = -3.4028234663852886e38f;
+                hi_last = 3.4028234663852886e38f;
+                n_prev = -2;
+                continue;
             }
             if (!final_pass && n == n_prev) {               // the last bounds removed nothing: converged, evaluate the survivors
                 n_prev = -2;
@@ -579,6 +595,7 @@ extern "C" int apgpu_box_clipped_stats_f32(const float *data, const uint8_t *mas
     if (box_height < 1 || box_width < 1 || (int64_t)box_height * box_width > (1 << 24))
         return fail(APGPU_EINVAL, "box_clipped_stats: bad box size %d x %d", box_height, box_width);
     if (!(sigma >= 0.0) || maxiters < 0) return fail(APGPU_EINVAL, "box_clipped_stats: bad clip parameters");
+    if (maxiters == 0) maxiters = 0x7fffffff;               // SigmaClip stores `maxiters or np.inf`: 0 clips until nothing changes
     const int ny = (int)((height + box_height - 1) / box_height), nx = (int)((width + box_width - 1) / box_width);
     const int64_t npix = (int64_t)box_height * box_width;
     const dim3 grid((unsigned)(ny * nx));

@@ -420,7 +420,8 @@ extern "C" int apgpu_lacosmic_iterate(float *clean, const uint8_t *mask, uint8_t
                                       int64_t *ncr_out, void *ws, size_t ws_bytes, void *stream)
 {
     if (!clean || !crmask || !ncr_out || !ws) return fail(APGPU_EINVAL, "lacosmic_iterate: NULL pointer argument");
-    if (height < 5 || width < 5 || height > 0x7fffffff || width > 0x7fffffff) return fail(APGPU_EINVAL, "lacosmic_iterate: bad shape");
+    // (an image below 5 pixels on a side has no pixel 2 away from every border: cosmic rays are flagged, none is cleaned)
+    if (height <= 0 || width <= 0 || height > 0x7fffffff || width > 0x7fffffff) return fail(APGPU_EINVAL, "lacosmic_iterate: bad shape");
     if (ws_bytes < apgpu_lacosmic_ws_bytes(height, width)) return fail(APGPU_EWORKSPACE, "lacosmic_iterate: workspace too small");
     hipStream_t st = as_stream(stream);
     const int H = (int)height, W = (int)width;

@@ -7,6 +7,8 @@ pins photutils>=1.10) and no reference test covers this class, so nothing here c
 own output: the functions restate photutils' published algorithms with NumPy / SciPy (scipy.ndimage supplies label,
 binary_dilation, generic_filter and zoom - the very routines photutils calls) and the pinned sigma-clip of oracle/apref.c.
 The HIP kernels are tested against THIS file; agreement with photutils itself is unverified.
+Exception: box_clipped_stats is PINNED - golden group G15 (tests/golden/make_golden_boxstats.py) holds it to astropy's own
+SigmaClip + np.nanmedian / np.nanstd, the calls Background2D makes per box.
 """
 import numpy as np
 from scipy import ndimage
@@ -38,7 +40,8 @@ def make_source_mask(data, nsigma=2.0, npixels=5, dilate_size=13):
 
 def box_clipped_stats(data, mask, box_h, box_w, sigma=3.0, maxiters=5):
     """Per-box SigmaClip(sigma, maxiters) + nanmedian / nanstd (Background2D with MedianBackground; edge_method 'pad':
-    the image is padded with masked pixels to whole boxes).  Returns (median, std, nfinal, nmasked0) as [ny, nx] arrays."""
+    the image is padded with masked pixels to whole boxes).  Returns (median, std, nfinal, nmasked0) as [ny, nx] arrays.
+    maxiters=0 clips until nothing changes, like None: SigmaClip stores `maxiters or np.inf` (golden group G15 records it)."""
     H, W = data.shape
     ny, nx = -(-H // box_h), -(-W // box_w)
     pad = np.full((ny * box_h, nx * box_w), np.nan, np.float32)
@@ -48,7 +51,7 @@ def box_clipped_stats(data, mask, box_h, box_w, sigma=3.0, maxiters=5):
         m[:H, :W] = np.asarray(mask) != 0
         pad[m] = np.nan
     boxes = pad.reshape(ny, box_h, nx, box_w).transpose(1, 3, 0, 2).reshape(box_h * box_w, ny, nx)
-    r = apref.stack_sigclip(np.ascontiguousarray(boxes), sigma=sigma, maxiters=maxiters, want=('median', 'std', 'count'))
+    r = apref.stack_sigclip(np.ascontiguousarray(boxes), sigma=sigma, maxiters=maxiters or None, want=('median', 'std', 'count'))
     nmasked0 = np.isnan(boxes).sum(0)
     return r['median'], r['std'], r['count'].astype(np.int64), nmasked0.astype(np.int64)
 

@@ -99,8 +99,9 @@ def satmask(data, inmask, satlevel):
     return sat
 
 
-def iterate(clean, mask, crmask, sigclip, sigfrac, objlim, readnoise, psfk, background):
-    """One detect_cosmics iteration, in place on clean / crmask; returns the number of cosmic-ray pixels found."""
+def iterate(clean, mask, crmask, sigclip, sigfrac, objlim, readnoise, psfk, background, info=None):
+    """One detect_cosmics iteration, in place on clean / crmask; returns the number of cosmic-ray pixels found.  `info`
+    (a dict) collects the pixels that had no good neighbour and took the background level, in info['background_pixels']."""
     s = laplace_rebin(clean)
     m5 = np.maximum(sepmedfilt(clean, 7), F(0.00001))
     noise = np.sqrt(m5 + F(readnoise) * F(readnoise))
@@ -127,13 +128,17 @@ def iterate(clean, mask, crmask, sigclip, sigfrac, objlim, readnoise, psfk, back
                     tot = F(tot + src[r + dy, c + dx])
                     cnt += 1
         clean[r, c] = F(tot / F(cnt)) if cnt > 0 else F(background)
+        if cnt == 0 and info is not None:
+            info.setdefault('background_pixels', []).append((int(r), int(c)))
     return n
 
 
 def detect_cosmics(data, gain=1.0, sigclip=4.5, sigfrac=0.3, objlim=5.0, readnoise=12.0, satlevel=65535.0, niter=6, psffwhm=3.5,
-                   fsmode='convolve', inmask=None):
+                   fsmode='convolve', inmask=None, return_info=False):
     """ccdproc.cosmicray_lacosmic(data, gain_apply=True, ...) as ApFixCosmicRays calls it: (cleaned image in ELECTRONS, float32;
-    crmask bool).  Non-finite pixels are zeroed and masked (the kernels' contract; astroscrappy would propagate NaN)."""
+    crmask bool).  Non-finite pixels are zeroed and masked (the kernels' contract; astroscrappy would propagate NaN).
+    return_info=True appends a dict: niter (iterations run, the one that found nothing included), mask (saturation + grown
+    input mask), background, background_pixels (cosmic rays without a good neighbour, set to the background level)."""
     clean = (np.asarray(data) * gain).astype(F)
     nonfinite = ~np.isfinite(clean)
     clean[nonfinite] = F(0)
@@ -143,7 +148,11 @@ def detect_cosmics(data, gain=1.0, sigclip=4.5, sigfrac=0.3, objlim=5.0, readnoi
     background = F(np.median(goodvals)) if goodvals.size else F(0)
     psfk = gausskernel(psffwhm, 7) if fsmode == 'convolve' else None
     crmask = np.zeros(clean.shape, bool)
+    info = dict(niter=0, mask=mask, background=background, background_pixels=[])
     for _ in range(niter):
-        if iterate(clean, mask, crmask, sigclip, sigfrac, objlim, readnoise, psfk, background) == 0:
+        info['niter'] += 1
+        if iterate(clean, mask, crmask, sigclip, sigfrac, objlim, readnoise, psfk, background, info) == 0:
             break
+    if return_info:
+        return clean, crmask, info
     return clean, crmask

@@ -1,7 +1,9 @@
 """F4 (first half): the sky-background mesh of ApMeasureBackground on the GPU against oracle/background_ref.py - a
 NumPy / SciPy restatement of the photutils algorithms the reference calls.  photutils is absent from the build container:
-parity with the reference's own output is UNPINNED (the oracle header says so); these tests pin the kernels to the
-restatement, and the spline evaluation to scipy.ndimage.zoom itself."""
+parity of its mesh glue (source detection, exclude_percentile, IDW fill, mesh filter) with the reference's own output is
+UNPINNED (the oracle header says so); these tests pin the kernels to the restatement, and the spline evaluation to
+scipy.ndimage.zoom itself.  PINNED elsewhere: the per-box clip, median and std to astropy itself (golden group G15,
+tests/test_gpu_boxstats_golden.py), the source mask to scipy.ndimage on adversarial patterns (tests/test_gpu_source_mask.py)."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,8 @@
 """F4 (second half): L.A.Cosmic on the GPU against oracle/lacosmic_ref.py - a restatement of astroscrappy's detect_cosmics
 as ccdproc.cosmicray_lacosmic runs it for ApFixCosmicRays.  ccdproc / astroscrappy are absent from the build container:
-parity with the reference's own output is UNPINNED; these tests pin the kernels to the restatement, bit for bit."""
+parity with astroscrappy's own output stays UNPINNED; these tests pin the kernels to the restatement, bit for bit.  The
+restatement's helpers (median filter, dilations, convolution, Laplacian) are held to scipy.ndimage by
+tests/test_oracle_lacosmic_scipy.py; borders, parameters, input masks and odd shapes are in tests/test_gpu_lacosmic_edges.py."""
 import numpy as np
 import pytest
 
