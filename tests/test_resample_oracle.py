@@ -34,6 +34,8 @@ def test_identity_and_integer_shift_are_exact():
 
 
 def test_matches_direct_float64_lanczos():
+    """A loose check (1.5e-3 on values near 100: sized to the phase quantisation).  The tight one - exact coordinates, phases and
+    defined pixels, values to c * 2^-24 * S of a float64 evaluation with the same table - is tests/test_resample_model_host.py."""
     yy, xx = np.mgrid[0:80, 0:90]
     img = (100 + 20 * np.sin(xx / 7.0) + 15 * np.cos(yy / 5.0) + 0.1 * xx).astype(np.float32)
     A = np.array([[np.cos(0.003), -np.sin(0.003), 1.37, np.sin(0.003), np.cos(0.003), 0.61]])
