@@ -5,6 +5,8 @@ a GPU; the .so is written next to this file so that it travels with the source t
 """
 import concurrent.futures as cf
 import os
+import re
+import shlex
 import subprocess
 import sys
 
@@ -14,73 +16,23 @@ CSRC = os.path.join(PKG, 'csrc')
 OBJ = os.path.join(CSRC, '_obj')
 LIB = os.path.join(PKG, 'libapgpu.so')
 
-SOURCES = ['common.hip', 'elementwise.hip', 'fixbadpix.hip', 'sigclip_global.hip', 'resample.hip', 'resample_stack.hip', 'stack.hip', 'stack_big.hip', 'stack_chunks.hip', 'stack_mad.hip', 'stack_mad_wide.hip', 'stack_mad_pairs.hip', 'stack_mad_pairs_wide.hip', 'combine_f64.hip', 'background.hip', 'lacosmic.hip', 'autobadcol.hip'] + [
-    'stack_inst_f32_calib_h.hip',
-    'stack_inst_f32_plain_h.hip',
-    'stack_inst_u16_calib_h.hip',
-    'stack_inst_u16_plain_h.hip',
-    'stack_inst_f32_calib_o.hip',
-    'stack_inst_f32_plain_o.hip',
-    'stack_inst_u16_calib_o.hip',
-    'stack_inst_u16_plain_o.hip',
-    'stack_inst_f32_calib_g.hip',
-    'stack_inst_f32_plain_g.hip',
-    'stack_inst_u16_calib_g.hip',
-    'stack_inst_u16_plain_g.hip',
-    'stack_inst_f32_calib_j.hip',
-    'stack_inst_f32_plain_j.hip',
-    'stack_inst_u16_calib_j.hip',
-    'stack_inst_u16_plain_j.hip',
-    'stack_inst_f32_calib_f.hip',
-    'stack_inst_f32_plain_f.hip',
-    'stack_inst_u16_calib_f.hip',
-    'stack_inst_u16_plain_f.hip',
-    'stack_inst_f32_calib_n.hip',
-    'stack_inst_f32_plain_n.hip',
-    'stack_inst_u16_calib_n.hip',
-    'stack_inst_u16_plain_n.hip',
-    'stack_inst_f32_calib_e.hip',
-    'stack_inst_f32_plain_e.hip',
-    'stack_inst_u16_calib_e.hip',
-    'stack_inst_u16_plain_e.hip',
-    'stack_inst_f32_calib_i.hip',
-    'stack_inst_f32_plain_i.hip',
-    'stack_inst_u16_calib_i.hip',
-    'stack_inst_u16_plain_i.hip',
-    'stack_inst_f32_calib_d.hip',
-    'stack_inst_f32_plain_d.hip',
-    'stack_inst_u16_calib_d.hip',
-    'stack_inst_u16_plain_d.hip',
-    'stack_inst_f32_calib_m.hip',
-    'stack_inst_f32_plain_m.hip',
-    'stack_inst_u16_calib_m.hip',
-    'stack_inst_u16_plain_m.hip',
-    'stack_inst_f32_calib_c.hip',
-    'stack_inst_f32_plain_c.hip',
-    'stack_inst_u16_calib_c.hip',
-    'stack_inst_u16_plain_c.hip',
-    'stack_inst_f32_calib_l.hip',
-    'stack_inst_f32_plain_l.hip',
-    'stack_inst_u16_calib_l.hip',
-    'stack_inst_u16_plain_l.hip',
-    'stack_inst_f32_calib_b.hip',
-    'stack_inst_f32_plain_b.hip',
-    'stack_inst_u16_calib_b.hip',
-    'stack_inst_u16_plain_b.hip',
-    'stack_inst_f32_calib_k.hip',
-    'stack_inst_f32_plain_k.hip',
-    'stack_inst_u16_calib_k.hip',
-    'stack_inst_u16_plain_k.hip',
-    'stack_inst_f32_calib_a.hip',
-    'stack_inst_f32_plain_a.hip',
-    'stack_inst_u16_calib_a.hip',
-    'stack_inst_u16_plain_a.hip']
-HEADERS = ['common.h', 'stack_sort.h', 'stack_calibrate.h', 'stack_reduce.h', 'stack_kernels.h', os.path.join(ROOT, 'include', 'apgpu.h')]
+# The translation units, in link order.  First the ones that are a source file each ...
+UNITS = ['common', 'elementwise', 'fixbadpix', 'sigclip_global', 'resample', 'resample_stack', 'stack', 'stack_big', 'stack_chunks',
+         'stack_mad', 'stack_mad_wide', 'stack_mad_pairs', 'stack_mad_pairs_wide', 'combine_f64', 'background', 'lacosmic', 'autobadcol']
+# ... then the register-resident stack kernels: stack_inst.hip once per slot group x raw dtype x fused calibration (the groups'
+# slot counts: the table in stack_calibrate.h).  The groups are linked in the fatbinary order of the library the recorded
+# measurements were taken with (largest slot counts first): a kernel's place in the loaded code is kept with it.
+STACK_GROUPS = ['h', 'o', 'g', 'j', 'f', 'n', 'e', 'i', 'd', 'm', 'c', 'l', 'b', 'k', 'a']
+STACK_DTYPES = [('f32', 'float'), ('u16', 'uint16_t')]
+STACK_CALIB = [('calib', 'true'), ('plain', 'false')]
 
 # -ffp-contract=off: the reference's NumPy expressions round after every operation, so no FMA
 # contraction anywhere; fused operations are written explicitly (fma()) where wanted.
-HIPCC_FLAGS = (['-DAPGPU_DEVELOPMENT'] if os.environ.get('APGPU_DEVELOPMENT') else []) + ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off',
-               '-fno-fast-math', '-Wall', '-Wno-unused-function', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC]
+HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math', '-Wall',
+               '-Wno-unused-function', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC]
+# The stack kernels' translation units: machine LICM off - the complete lean kernel is one loop (plain launch and redo pass share
+# its body) and hoisted loop-invariant values cost it 5-10 VGPRs, the difference between three and two wavefronts per SIMD.
+STACK_TU_FLAGS = ['-mllvm', '-disable-machine-licm']
 
 
 def _hipcc():
@@ -90,32 +42,45 @@ def _hipcc():
     return 'hipcc'
 
 
-def _newest(paths):
-    return max(os.path.getmtime(p if os.path.isabs(p) else os.path.join(CSRC, p)) for p in paths)
+def compile_units(obj_dir=OBJ):
+    """Yields (unit name, source, full compile command) in link order; the object is <obj_dir>/<unit name>.o, and the compiler
+    writes the files it read next to it (<unit name>.d)."""
+    base = [_hipcc()] + (['-DAPGPU_DEVELOPMENT'] if os.environ.get('APGPU_DEVELOPMENT') else []) + HIPCC_FLAGS
+    units = [(u, u, STACK_TU_FLAGS if u == 'resample_stack' else []) for u in UNITS]
+    units += [('stack_inst_%s_%s_%s' % (tag, ctag, g), 'stack_inst',
+               STACK_TU_FLAGS + ['-DAPGPU_INST_RAW=' + raw, '-DAPGPU_INST_CALIB=' + calib, '-DAPGPU_INST_GROUP=' + g])
+              for g in STACK_GROUPS for tag, raw in STACK_DTYPES for ctag, calib in STACK_CALIB]
+    for name, src, flags in units:
+        stem = os.path.join(obj_dir, name)
+        srcp = os.path.join(CSRC, src + '.hip')
+        yield name, srcp, base + flags + ['-MD', '-MF', stem + '.d', '-c', srcp, '-o', stem + '.o']
 
 
-# The stack kernels' translation units: machine LICM off - the complete lean kernel is one loop (plain launch and redo pass share
-# its body) and hoisted loop-invariant values cost it 5-10 VGPRs, the difference between three and two wavefronts per SIMD.
-STACK_TU_FLAGS = ['-mllvm', '-disable-machine-licm']
+def _up_to_date(obj, cmdline):
+    """The object is newer than every file the compiler read for it, and was made by this very command line."""
+    try:
+        if open(obj[:-2] + '.cmd').read() != cmdline:
+            return False
+        deps = open(obj[:-2] + '.d').read().replace('\\\n', ' ').split(': ', 1)[1]
+        built = os.path.getmtime(obj)
+        return all(os.path.getmtime(d.replace('\\ ', ' ')) <= built for d in re.split(r'(?<!\\)\s+', deps.strip()))
+    except (OSError, IndexError):                            # no object, stamp or dependency file, or a file it names is gone
+        return False
 
 
-def _compile(src):
-    obj = os.path.join(OBJ, src.replace('.hip', '.o'))
-    srcp = os.path.join(CSRC, src)
-    extra = ['stack_mad.h'] if src.startswith('stack_mad') else []
-    if src.startswith('resample'):
-        extra.append('resample_core.h')
-    if src == 'stack_mad_wide.hip':
-        extra.append('stack_mad.hip')                        # (the wide units include the narrow ones)
-    if src == 'stack_mad_pairs_wide.hip':
-        extra.append('stack_mad_pairs.hip')
-    dep_time = max(os.path.getmtime(srcp), _newest(HEADERS + extra))
-    if os.path.exists(obj) and os.path.getmtime(obj) >= dep_time:
+def _compile(unit):
+    name, _, cmd = unit
+    obj, cmdline = cmd[-1], shlex.join(cmd)
+    if _up_to_date(obj, cmdline):
         return obj, False
-    cmd = [_hipcc()] + HIPCC_FLAGS + (STACK_TU_FLAGS if src.startswith(('stack_inst_', 'resample_stack')) else []) + ['-c', srcp, '-o', obj]
+    stamp = obj[:-2] + '.cmd'
+    if os.path.exists(stamp):
+        os.remove(stamp)                                     # (an interrupted compile leaves no stamp: built again)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError('hipcc failed for %s:\n%s' % (src, r.stdout[-4000:]))
+        raise RuntimeError('hipcc failed for %s:\n%s' % (name, r.stdout[-4000:]))
+    with open(stamp, 'w') as fh:
+        fh.write(cmdline)
     return obj, True
 
 
@@ -124,12 +89,13 @@ def build_library(force=False, verbose=False, jobs=None):
     if force:
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
-    jobs = jobs or min(len(SOURCES), os.cpu_count() or 4)
+    units = list(compile_units())
+    jobs = jobs or int(os.environ.get('MAX_JOBS') or 0) or min(len(units), os.cpu_count() or 4, 16)
     with cf.ThreadPoolExecutor(jobs) as ex:
-        results = list(ex.map(_compile, SOURCES))
+        results = list(ex.map(_compile, units))
     objs = [o for o, _ in results]
     rebuilt = any(r for _, r in results)
-    if rebuilt or not os.path.exists(LIB):
+    if rebuilt or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(map(os.path.getmtime, objs)):
         cmd = [_hipcc(), '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + objs
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
@@ -140,4 +106,9 @@ def build_library(force=False, verbose=False, jobs=None):
 
 
 if __name__ == '__main__':
-    build_library(force='--force' in sys.argv, verbose=True)
+    if '--commands' in sys.argv:                             # one line per unit: name, source, command (for tools/*.sh)
+        obj_dir = sys.argv[sys.argv.index('--obj-dir') + 1] if '--obj-dir' in sys.argv else OBJ
+        for name, src, cmd in compile_units(obj_dir):
+            print('%s\t%s\t%s' % (name, src, shlex.join(cmd)))
+    else:
+        build_library(force='--force' in sys.argv, verbose=True)

@@ -1,6 +1,6 @@
 // stack.hip - argument checking and dispatch for the stack reductions (kernels: stack_kernels.h,
-// instantiated per raw dtype / fused-calibration flag / slot-count group in stack_inst_*.hip so that they
-// build in parallel).
+// instantiated by stack_inst.hip, which is compiled once per raw dtype / fused-calibration flag / group of slot
+// counts - the table in stack_calibrate.h - so that they build in parallel).
 #include "stack_kernels.h"
 
 #include <cstdlib>

@@ -33,7 +33,35 @@ struct StackParams {
     int unclipped_nonfinite; // rich kernels only: a column holding a non-finite value is not clipped (APGPU_STACK_NONFINITE_UNCLIPPED)
 };
 
-// The slot counts the dispatcher uses (launch_np) and, for each, the largest N that still selects the previous one: a
+// THE SLOT COUNTS of the register-resident stack kernels, each written once, under the group it is compiled in: every multiple
+// of 4 up to 64, every multiple of 8 from there to 128 (round 4: a stack between two slot counts runs the padded kernel, which
+// costs more than the next full one - so the gaps are at most 3 / 7 frames wide).  A group is one translation unit per raw dtype
+// and calibration flag (stack_inst.hip compiled with -DAPGPU_INST_GROUP=<letter>; _build.py knows the letters, nothing else);
+// APGPU_SLOT_GROUPS lists the groups in ascending order of their counts.  prev_slots(), the declarations of launch_one and the
+// dispatch of launch_np (stack_kernels.h) all expand this table.
+#define APGPU_SLOTS_a(X) X(1) X(4) X(8) X(12) X(16)
+#define APGPU_SLOTS_k(X) X(20) X(24) X(28)
+#define APGPU_SLOTS_b(X) X(32) X(36)
+#define APGPU_SLOTS_l(X) X(40) X(44)
+#define APGPU_SLOTS_c(X) X(48) X(52)
+#define APGPU_SLOTS_m(X) X(56) X(60)
+#define APGPU_SLOTS_d(X) X(64)
+#define APGPU_SLOTS_i(X) X(72)
+#define APGPU_SLOTS_e(X) X(80)
+#define APGPU_SLOTS_n(X) X(88)
+#define APGPU_SLOTS_f(X) X(96)
+#define APGPU_SLOTS_j(X) X(104)
+#define APGPU_SLOTS_g(X) X(112)
+#define APGPU_SLOTS_o(X) X(120)
+#define APGPU_SLOTS_h(X) X(128)
+#define APGPU_SLOT_GROUPS(X)                                                                                                  \
+    APGPU_SLOTS_a(X) APGPU_SLOTS_k(X) APGPU_SLOTS_b(X) APGPU_SLOTS_l(X) APGPU_SLOTS_c(X) APGPU_SLOTS_m(X) APGPU_SLOTS_d(X)    \
+    APGPU_SLOTS_i(X) APGPU_SLOTS_e(X) APGPU_SLOTS_n(X) APGPU_SLOTS_f(X) APGPU_SLOTS_j(X) APGPU_SLOTS_g(X) APGPU_SLOTS_o(X)    \
+    APGPU_SLOTS_h(X)
+#define APGPU_SLOT_THEN_COMMA(NP) NP,
+#define APGPU_COMMA_THEN_SLOT(NP) , NP
+
+// For each slot count, the largest N that still selects the previous one (launch_np takes the first count >= N): a
 // stack that runs with NP slots has more than prev_slots(NP) frames, so only the slots from there on can be padding.
 // Padded stacks of 112 / 120 / 128 slots (round 4: 112 and 120 too - with the skipping scheme they take 258 VGPRs, one wavefront
 // per SIMD) keep the older scheme (every slot loaded and calibrated, padding lifted to +inf with
@@ -43,7 +71,7 @@ constexpr int padded_minn(int np, bool full) { return (full || np >= 112) ? np :
 
 constexpr int prev_slots(int np)
 {
-    constexpr int counts[] = {1, 4, 8, 12, 16, 20, 24, 28, 32, 36, 40, 44, 48, 52, 56, 60, 64, 72, 80, 88, 96, 104, 112, 120, 128};
+    constexpr int counts[] = {APGPU_SLOT_GROUPS(APGPU_SLOT_THEN_COMMA)};
     int prev = 0;
     for (int c : counts) {
         if (c >= np) break;
@@ -51,6 +79,9 @@ constexpr int prev_slots(int np)
     }
     return prev;
 }
+#define APGPU_SLOT_ASCENDS(NP) static_assert(prev_slots(NP) < NP && prev_slots(NP + 1) == NP, "APGPU_SLOT_GROUPS: ascending slot counts");
+APGPU_SLOT_GROUPS(APGPU_SLOT_ASCENDS)
+#undef APGPU_SLOT_ASCENDS
 
 __device__ __forceinline__ float to_f32(float x) { return x; }
 __device__ __forceinline__ float to_f32(uint16_t x) { return (float)x; }

@@ -1024,6 +1024,20 @@ int launch_fast_u16_pairs(const StackParams &prm0, dim3 grid, hipStream_t st)
         [&](const StackParams &q, unsigned wgs) { hipLaunchKernelGGL((stack_sigclip_kernel<NP, uint16_t, CALIB, false, FULL, false>), dim3(wgs), dim3(256), 0, st, q); });
 }
 
+// One instantiation per pad count: calls launch(std::integral_constant<int, K>) for the K of 0 .. the sequence's last that
+// equals `pads` (0: a full stack).  The launcher decides with `if constexpr` which pad counts have a kernel and answers
+// kNoRedoList for the others, as this does for a pad count outside the sequence.
+template <typename Launch, int... K>
+int launch_by_pads(int pads, Launch launch, std::integer_sequence<int, K...>)
+{
+    // (from the largest pad count down: the compiler emits the kernels that one expression instantiates last first, and in
+    // the code objects they stand in ascending order - a kernel's place in the loaded code is part of what was measured)
+    constexpr int kLast = sizeof...(K) - 1;
+    int rc = kNoRedoList;
+    (void)((pads == kLast - K ? (rc = launch(std::integral_constant<int, kLast - K>{}), true) : false) || ...);
+    return rc;
+}
+
 // `describe` != nullptr: write the name of the kernel variant this call would launch (as rocprofv3 prints it, without
 // the namespace) into describe[0..255] and launch nothing - the bench line and the profiles name the dominant kernel
 // from the dispatch itself instead of a literal.
@@ -1032,6 +1046,8 @@ int launch_one(const StackParams &prm, bool median_only, hipStream_t st, char *d
 {
     const char *rawname = sizeof(RawT) == 2 ? "unsigned short" : "float";
     const char *tf[2] = {"false", "true"};
+    constexpr int kMaxPads = NP - prev_slots(NP) - 1;                // (the next smaller slot count serves fewer frames)
+    constexpr auto kPadCounts = std::make_integer_sequence<int, kMaxPads + 1>{};
     if constexpr (sizeof(RawT) == 2) {
         // uint16 median: pixel pairs per lane need 4-byte aligned frame rows and 8-byte aligned planes
         const bool pairs = median_only && (prm.P % 2 == 0) && (prm.stride % 2 == 0) &&
@@ -1062,21 +1078,12 @@ int launch_one(const StackParams &prm, bool median_only, hipStream_t st, char *d
                 return APGPU_OK;
             }
             if (!describe && fastp) {
-                int frc = kNoRedoList;
-                if constexpr (kFastPairsFull) {
-                    if (prm.N == NP) frc = launch_fast_u16_pairs<NP, CALIB, true>(prm, dim3((unsigned)grid), st);
-                }
-                if constexpr (kFastPairsPadded) {            // (1 .. 3 pads up to 64 slots, 1 .. 7 beyond: one instantiation each)
-                    if (prm.N == NP - 1) frc = launch_fast_u16_pairs<NP, CALIB, false, 1>(prm, dim3((unsigned)grid), st);
-                    if (prm.N == NP - 2) frc = launch_fast_u16_pairs<NP, CALIB, false, 2>(prm, dim3((unsigned)grid), st);
-                    if (prm.N == NP - 3) frc = launch_fast_u16_pairs<NP, CALIB, false, 3>(prm, dim3((unsigned)grid), st);
-                    if constexpr (NP > 64) {
-                        if (prm.N == NP - 4) frc = launch_fast_u16_pairs<NP, CALIB, false, 4>(prm, dim3((unsigned)grid), st);
-                        if (prm.N == NP - 5) frc = launch_fast_u16_pairs<NP, CALIB, false, 5>(prm, dim3((unsigned)grid), st);
-                        if (prm.N == NP - 6) frc = launch_fast_u16_pairs<NP, CALIB, false, 6>(prm, dim3((unsigned)grid), st);
-                        if (prm.N == NP - 7) frc = launch_fast_u16_pairs<NP, CALIB, false, 7>(prm, dim3((unsigned)grid), st);
-                    }
-                }
+                // (padded: 1 .. 3 pads up to 64 slots, 1 .. 7 beyond - kMaxPads of the slot counts of pairs_padded_slots)
+                const int frc = launch_by_pads(NP - prm.N, [&](auto k) {
+                    constexpr int K = decltype(k)::value;
+                    if constexpr (K == 0 ? kFastPairsFull : kFastPairsPadded) return launch_fast_u16_pairs<NP, CALIB, K == 0, K>(prm, dim3((unsigned)grid), st);
+                    else return kNoRedoList;
+                }, kPadCounts);
                 if (frc != kNoRedoList) return frc;
             }
         }
@@ -1111,7 +1118,6 @@ int launch_one(const StackParams &prm, bool median_only, hipStream_t st, char *d
     // the fast kernel + redo list (see stack_fast_kernel): float32 stacks on the float32 fast path, lean outputs, no pedestals
     // (uint16 frames: only the cases of `wide_fast` above - everything else went to the pair kernels)
     constexpr bool kFastSlots = (sizeof(RawT) == 4 || CALIB) && fast_kernel_slots(NP);
-    constexpr int kMaxPads = NP - prev_slots(NP) - 1;                // (the next smaller slot count serves fewer frames)
     // mean + median + std planes (PLUS, up to 96 slots) have their fast kernel too: float32 stacks of any frame count, uint16
     // stacks (fused calibration, one pixel per lane) when full
     constexpr bool kPlusSlots = NP <= 96 && (sizeof(RawT) == 4 || CALIB);
@@ -1132,33 +1138,18 @@ int launch_one(const StackParams &prm, bool median_only, hipStream_t st, char *d
     plain.redo = nullptr;
     if constexpr (kFastSlots) {
         int frc = kNoRedoList;
-        const int pads = NP - prm.N;
-        if (fastk && fastplus) {
-            if constexpr (kPlusSlots) {
-                if (pads == 0) frc = launch_fast<NP, RawT, CALIB, true, 0, true>(prm, g, st);
-                if constexpr (sizeof(RawT) == 4) {
-                    if constexpr (kMaxPads >= 1) if (pads == 1) frc = launch_fast<NP, RawT, CALIB, false, 1, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 2) if (pads == 2) frc = launch_fast<NP, RawT, CALIB, false, 2, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 3) if (pads == 3) frc = launch_fast<NP, RawT, CALIB, false, 3, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 4) if (pads == 4) frc = launch_fast<NP, RawT, CALIB, false, 4, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 5) if (pads == 5) frc = launch_fast<NP, RawT, CALIB, false, 5, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 6) if (pads == 6) frc = launch_fast<NP, RawT, CALIB, false, 6, true>(prm, g, st);
-                    if constexpr (kMaxPads >= 7) if (pads == 7) frc = launch_fast<NP, RawT, CALIB, false, 7, true>(prm, g, st);
-                }
-            }
-        } else if (fastk) {
-            if constexpr (sizeof(RawT) == 4 || NP > 112) {
-                if (pads == 0) frc = launch_fast<NP, RawT, CALIB, true>(prm, g, st);
-            }
-            if constexpr (sizeof(RawT) == 4 || NP > 64) {
-                if constexpr (kMaxPads >= 1) if (pads == 1) frc = launch_fast<NP, RawT, CALIB, false, 1>(prm, g, st);
-                if constexpr (kMaxPads >= 2) if (pads == 2) frc = launch_fast<NP, RawT, CALIB, false, 2>(prm, g, st);
-                if constexpr (kMaxPads >= 3) if (pads == 3) frc = launch_fast<NP, RawT, CALIB, false, 3>(prm, g, st);
-                if constexpr (kMaxPads >= 4) if (pads == 4) frc = launch_fast<NP, RawT, CALIB, false, 4>(prm, g, st);
-                if constexpr (kMaxPads >= 5) if (pads == 5) frc = launch_fast<NP, RawT, CALIB, false, 5>(prm, g, st);
-                if constexpr (kMaxPads >= 6) if (pads == 6) frc = launch_fast<NP, RawT, CALIB, false, 6>(prm, g, st);
-                if constexpr (kMaxPads >= 7) if (pads == 7) frc = launch_fast<NP, RawT, CALIB, false, 7>(prm, g, st);
-            }
+        if (fastk && fastplus) {                             // (uint16: full stacks only)
+            frc = launch_by_pads(NP - prm.N, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                if constexpr (kPlusSlots && (K == 0 || sizeof(RawT) == 4)) return launch_fast<NP, RawT, CALIB, K == 0, K, true>(prm, g, st);
+                else return kNoRedoList;
+            }, kPadCounts);
+        } else if (fastk) {                                  // (uint16: u16_lean_ok)
+            frc = launch_by_pads(NP - prm.N, [&](auto k) {
+                constexpr int K = decltype(k)::value;
+                if constexpr (sizeof(RawT) == 4 || NP > (K == 0 ? 112 : 64)) return launch_fast<NP, RawT, CALIB, K == 0, K>(prm, g, st);
+                else return kNoRedoList;
+            }, kPadCounts);
         }
         if (frc != kNoRedoList) return frc;
     }
@@ -1196,54 +1187,32 @@ int launch_one(const StackParams &prm, bool median_only, hipStream_t st, char *d
     return check_launch("stack kernel");
 }
 
-// launch_one<NP, RawT, CALIB> is explicitly instantiated in the stack_inst_*.hip translation units (one group of
-// slot counts each, so that the build parallelises); everybody else only sees these declarations.
+// launch_one<NP, RawT, CALIB> is explicitly instantiated by stack_inst.hip, compiled once per raw dtype, calibration flag and
+// group of slot counts (the table in stack_calibrate.h) so that the build parallelises; everybody else only sees these
+// declarations, one set per slot count of the table.
 #ifndef APGPU_STACK_INSTANTIATE
 #define APGPU_DECLARE_LAUNCH(NP)                                                                          \
     extern template int launch_one<NP, float, true>(const StackParams &, bool, hipStream_t, char *);      \
     extern template int launch_one<NP, float, false>(const StackParams &, bool, hipStream_t, char *);     \
     extern template int launch_one<NP, uint16_t, true>(const StackParams &, bool, hipStream_t, char *);   \
     extern template int launch_one<NP, uint16_t, false>(const StackParams &, bool, hipStream_t, char *);
-APGPU_DECLARE_LAUNCH(1) APGPU_DECLARE_LAUNCH(4) APGPU_DECLARE_LAUNCH(8) APGPU_DECLARE_LAUNCH(12) APGPU_DECLARE_LAUNCH(16)
-APGPU_DECLARE_LAUNCH(20) APGPU_DECLARE_LAUNCH(24) APGPU_DECLARE_LAUNCH(28) APGPU_DECLARE_LAUNCH(32) APGPU_DECLARE_LAUNCH(36)
-APGPU_DECLARE_LAUNCH(40) APGPU_DECLARE_LAUNCH(44) APGPU_DECLARE_LAUNCH(48) APGPU_DECLARE_LAUNCH(52) APGPU_DECLARE_LAUNCH(56)
-APGPU_DECLARE_LAUNCH(60) APGPU_DECLARE_LAUNCH(64) APGPU_DECLARE_LAUNCH(72) APGPU_DECLARE_LAUNCH(80) APGPU_DECLARE_LAUNCH(88)
-APGPU_DECLARE_LAUNCH(96) APGPU_DECLARE_LAUNCH(104) APGPU_DECLARE_LAUNCH(112) APGPU_DECLARE_LAUNCH(120) APGPU_DECLARE_LAUNCH(128)
+APGPU_SLOT_GROUPS(APGPU_DECLARE_LAUNCH)
 #undef APGPU_DECLARE_LAUNCH
 #endif
+
+// The first slot count >= N; the last one takes whatever is left.
+template <typename RawT, bool CALIB, int... NPS>
+int launch_np_seq(const StackParams &prm, bool median_only, hipStream_t st, char *describe, std::integer_sequence<int, NPS...>)
+{
+    int rc = APGPU_OK, left = sizeof...(NPS);
+    (void)((--left == 0 || prm.N <= NPS ? (rc = launch_one<NPS, RawT, CALIB>(prm, median_only, st, describe), true) : false) || ...);
+    return rc;
+}
 
 template <typename RawT, bool CALIB>
 int launch_np(const StackParams &prm, bool median_only, hipStream_t st, char *describe = nullptr)
 {
-    const int N = prm.N;
-    // slot counts: every multiple of 4 up to 64, every multiple of 8 from there to 128 (round 4: a stack between two slot
-    // counts runs the padded kernel, which costs more than the next full one - so the gaps are at most 3 / 7 frames wide)
-    if (N <= 1) return launch_one<1, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 4) return launch_one<4, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 8) return launch_one<8, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 12) return launch_one<12, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 16) return launch_one<16, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 20) return launch_one<20, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 24) return launch_one<24, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 28) return launch_one<28, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 32) return launch_one<32, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 36) return launch_one<36, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 40) return launch_one<40, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 44) return launch_one<44, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 48) return launch_one<48, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 52) return launch_one<52, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 56) return launch_one<56, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 60) return launch_one<60, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 64) return launch_one<64, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 72) return launch_one<72, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 80) return launch_one<80, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 88) return launch_one<88, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 96) return launch_one<96, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 104) return launch_one<104, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 112) return launch_one<112, RawT, CALIB>(prm, median_only, st, describe);
-    if (N <= 120) return launch_one<120, RawT, CALIB>(prm, median_only, st, describe);
-    return launch_one<128, RawT, CALIB>(prm, median_only, st, describe);
+    return launch_np_seq<RawT, CALIB>(prm, median_only, st, describe, std::integer_sequence<int APGPU_SLOT_GROUPS(APGPU_COMMA_THEN_SLOT)>{});
 }
-
 
 }  // namespace apgpu_stack

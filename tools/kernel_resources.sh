@@ -1,18 +1,16 @@
 #!/bin/bash
-# Register / scratch / LDS use of every kernel in libapgpu.so (compiles each translation unit to assembly):
+# Register / scratch / LDS use of every kernel in libapgpu.so (compiles each translation unit of the build, with the build's
+# flags, to assembly):
 #   bash tools/kernel_resources.sh > profiles/<round>/kernel_resources.csv
 REPO=$(cd "$(dirname "$0")/.." && pwd)
-CS=$REPO/astrophotography_amd/csrc
 TMP=$(mktemp -d)
+cd $REPO
+python3 -m astrophotography_amd._build --commands --obj-dir $TMP > $TMP/units
 echo "translation_unit,kernel,vgpr,sgpr_spill,vgpr_spill,scratch_bytes,lds_bytes"
-for src in $CS/*.hip; do
-  b=$(basename $src .hip)
-  EXTRA=""; case $b in stack_inst_*) EXTRA="-mllvm -disable-machine-licm";; esac     # as _build.py's STACK_TU_FLAGS
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math $EXTRA -S --cuda-device-only -I$CS -I$REPO/include $src -o $TMP/$b.s 2>/dev/null &
-done
-wait
-for src in $CS/*.hip; do
-  b=$(basename $src .hip)
+while IFS=$'\t' read -r b src cmd; do
+  echo "$cmd -S --cuda-device-only -o $TMP/$b.s 2>/dev/null"
+done < $TMP/units | xargs -P ${MAX_JOBS:-$(nproc)} -d '\n' -n 1 bash -c
+sort $TMP/units | while IFS=$'\t' read -r b src cmd; do
   python3 - $TMP/$b.s $b <<'PY'
 import re,sys
 txt=open(sys.argv[1]).read()
