@@ -21,6 +21,7 @@ _LAZY = {
     'ApMeasureBackground': ('.core.ApMeasureBackground', 'ApMeasureBackground'),
     'ApFixCosmicRays': ('.core.ApFixCosmicRays', 'ApFixCosmicRays'),
     'ApAutoBadcols': ('.core.ApAutoBadcols', 'ApAutoBadcols'),
+    'ApFindStars': ('.core.ApFindStars', 'ApFindStars'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -114,6 +114,13 @@ SIGNATURES = {
                                                  C.c_int64, C.c_int64, C.c_void_p]),
     'apgpu_block_mean_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     'apgpu_weighted_mean_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_daofind_convolve_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    'apgpu_local_peaks_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_daofind_measure': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_aperture_phot_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

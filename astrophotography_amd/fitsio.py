@@ -10,7 +10,9 @@ module implements exactly that subset:
 * data: BITPIX 8, 16, 32, 64, -32, -64, big-endian on disk; the unsigned-integer convention
   (BITPIX=16, BSCALE=1, BZERO=32768 -> uint16; likewise uint32/uint64) as astropy's ``uint=True``;
   any other BSCALE/BZERO is applied like astropy does (float32 for <=16-bit integers, float64 above);
-* extensions after the primary HDU are preserved verbatim on rewrite.
+* extensions after the primary HDU are preserved verbatim on rewrite;
+* binary tables with scalar columns of TFORM D, E, J, K and L (``write_table`` / ``read_table``: the source list of
+  ``ApFindStars``).
 """
 import os
 
@@ -451,6 +453,119 @@ def read_extension(path, extname):
         if pos <= start:
             break
     raise KeyError("Extension '%s' not found in %s." % (extname, path))
+
+
+# ---------------------------------------------------------------------------------------------------
+# Binary tables: the source list of ApFindStars (core/ApFindStars.py:627-678: an empty primary HDU carrying the keyword
+# dictionary, then BINTABLE extensions).  Scalar columns of TFORM D, E, J, K and L only.
+# ---------------------------------------------------------------------------------------------------
+_TFORM_DTYPE = {'D': '>f8', 'E': '>f4', 'J': '>i4', 'K': '>i8', 'L': 'S1'}
+
+
+def _tform_of(a):
+    a = np.asarray(a)
+    if a.ndim != 1:
+        raise TypeError('table columns must be 1-D, got shape %s' % (a.shape,))
+    if a.dtype == np.bool_:
+        return 'L'
+    if a.dtype == np.float64:
+        return 'D'
+    if a.dtype == np.float32:
+        return 'E'
+    if a.dtype in (np.int64, np.uint32):
+        return 'K'
+    if a.dtype.kind in 'iu' and a.dtype.itemsize <= 4:
+        return 'J'
+    raise TypeError('cannot write a table column of dtype %s (D, E, J, K and L only)' % a.dtype)
+
+
+def _bintable_hdu(name, columns, units=None, cards=None):
+    names = list(columns)
+    cols = [np.asarray(columns[n]) for n in names]
+    nrows = len(cols[0]) if cols else 0
+    if any(len(c) != nrows for c in cols):
+        raise ValueError('table columns differ in length')
+    forms = [_tform_of(c) for c in cols]
+    rec = np.zeros(nrows, dtype=[('f%d' % i, _TFORM_DTYPE[f]) for i, f in enumerate(forms)])
+    for i, (c, f) in enumerate(zip(cols, forms)):
+        rec['f%d' % i] = np.where(c, b'T', b'F') if f == 'L' else c
+    head = [Card('XTENSION', 'BINTABLE', 'binary table extension'), Card('BITPIX', 8, 'array data type'),
+            Card('NAXIS', 2, 'number of array dimensions'), Card('NAXIS1', rec.dtype.itemsize, 'length of dimension 1'),
+            Card('NAXIS2', nrows, 'length of dimension 2'), Card('PCOUNT', 0, 'number of group parameters'),
+            Card('GCOUNT', 1, 'number of groups'), Card('TFIELDS', len(names), 'number of table fields')]
+    for i, (n, f) in enumerate(zip(names, forms)):
+        head += [Card('TTYPE%d' % (i + 1), n), Card('TFORM%d' % (i + 1), f)]
+        if units and units.get(n):
+            head.append(Card('TUNIT%d' % (i + 1), units[n]))
+    head.append(Card('EXTNAME', name, 'extension name'))
+    for k, v in (cards or []):
+        head.append(Card(k, *v) if isinstance(v, tuple) else Card(k, v))
+    payload = rec.tobytes()
+    return Header(head).tostring().encode('ascii') + payload + b'\0' * ((-len(payload)) % BLOCK)
+
+
+def write_table(path, tables, header=None, overwrite=True):
+    """Writes an empty primary HDU with the cards of `header` (a Header, or a dict key -> value | (value, comment)), followed by
+    one BINTABLE extension per entry of `tables` = [(extname, {column: 1-D array}, {column: unit} or None, [(key, value), ...]
+    extra cards or None), ...].  float64 -> D, float32 -> E, integers up to 32 bits -> J, int64 -> K, bool -> L."""
+    if os.path.exists(path) and not overwrite:
+        raise OSError("File '%s' already exists." % path)
+    head = [Card('SIMPLE', True, 'conforms to FITS standard'), Card('BITPIX', 8, 'array data type'),
+            Card('NAXIS', 0, 'number of array dimensions'), Card('EXTEND', True, '')]
+    if isinstance(header, Header):
+        head += [c for c in header.cards if c.key not in ('SIMPLE', 'BITPIX', 'NAXIS', 'EXTEND')]
+    else:
+        for k, v in (header or {}).items():
+            head.append(Card(k.upper(), *v) if isinstance(v, tuple) else Card(k.upper(), v))
+    tmp = str(path) + '.tmp%d' % os.getpid()
+    with open(tmp, 'wb') as f:
+        f.write(Header(head).tostring().encode('ascii'))
+        for t in tables:
+            name, columns = t[0], t[1]
+            f.write(_bintable_hdu(name, columns, t[2] if len(t) > 2 else None, t[3] if len(t) > 3 else None))
+    os.replace(tmp, path)
+
+
+def read_table(path, extname):
+    """(columns dict name -> numpy array in file order, extension Header, primary Header) of the first BINTABLE extension
+    called `extname` (case-insensitive); columns of TFORM D, E, J, K, L (an optional repeat count of 1 is accepted)."""
+    _, prim = read(path, want_data=False)
+    raw = prim._tail
+    pos = 0
+    while pos < len(raw):
+        text = ''
+        while True:
+            block = raw[pos:pos + BLOCK].decode('ascii', 'replace')
+            if len(block) < BLOCK:
+                raise OSError('%s: extension header is truncated.' % path)
+            pos += BLOCK
+            text += block
+            if any(block[i:i + 8] == 'END     ' for i in range(0, BLOCK, 80)):
+                break
+        eh = Header.fromstring(text)
+        naxis = int(eh.get('NAXIS', 0))
+        count = int(np.prod([int(eh['NAXIS%d' % i]) for i in range(1, naxis + 1)])) if naxis > 0 else 0
+        nbytes = count * abs(int(eh['BITPIX'])) // 8 + int(eh.get('PCOUNT', 0))
+        if str(eh.get('EXTNAME', '')).strip().upper() == extname.upper() and str(eh.get('XTENSION', '')).strip() == 'BINTABLE':
+            fields = []
+            for i in range(1, int(eh['TFIELDS']) + 1):
+                form = str(eh['TFORM%d' % i]).strip()
+                code = form.lstrip('1')
+                if code not in _TFORM_DTYPE:
+                    raise OSError('%s: unsupported TFORM%d = %r' % (path, i, form))
+                fields.append((str(eh['TTYPE%d' % i]).strip(), code))
+            dt = np.dtype([('f%d' % i, _TFORM_DTYPE[c]) for i, (_, c) in enumerate(fields)])
+            nrows = int(eh['NAXIS2'])
+            if dt.itemsize != int(eh['NAXIS1']) or len(raw) < pos + nrows * dt.itemsize:
+                raise OSError('%s: table %s is malformed or truncated.' % (path, extname))
+            rec = np.frombuffer(raw, dtype=dt, count=nrows, offset=pos)
+            cols = {}
+            for i, (n, c) in enumerate(fields):
+                v = rec['f%d' % i]
+                cols[n] = (v == b'T') if c == 'L' else v.astype(v.dtype.newbyteorder('='))
+            return cols, eh, prim
+        pos += ((nbytes + BLOCK - 1) // BLOCK) * BLOCK
+    raise KeyError("Table '%s' not found in %s." % (extname, path))
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1204,3 +1204,213 @@ def lacosmic(data_electrons, inmask=None, sigclip=4.5, sigfrac=0.3, objlim=5.0, 
         if int(ncr.item()) == 0:
             break
     return clean, crmask, it
+
+
+# ---------------------------------------------------------------------------------------------------
+# F6: star finding (core/ApFindStars.py:299-340, 363-446; photutils' DAOStarFinder / find_peaks / aperture_photometry
+# restated in tests/findstars_model.py, parity unpinned)
+# ---------------------------------------------------------------------------------------------------
+DAOFIND_RECORD = ('x_peak', 'y_peak', 'npix', 'peak', 'conv_peak', 'sharpness', 'roundness1', 'roundness2', 'dx', 'dy', 'hx', 'hy',
+                  'xcentroid', 'ycentroid', 'flux', 'mag')
+DAOFIND_MAX_RADIUS = 12
+
+
+def daofind_kernel(fwhm, device=None):
+    """The zero-sum DAOFIND kernel for a circular Gaussian of the given FWHM (sigma_radius 1.5, photutils' defaults) and
+    the constants of the marginal fits, built in float64 on the host.
+
+    dict(fwhm, sigma, R, K [2R+1, 2R+1] float64, fp bool footprint, npixels, relerr, p, consts{x, y}, tables [6, (2R+1)^2],
+    quad [2R+1, 2R+1]); with `device` also dev = dict(K, fp (uint8), tables, quad) of device tensors."""
+    import math
+    fwhm = float(fwhm)
+    if not fwhm > 0:
+        raise ValueError('fwhm must be positive, got %r' % (fwhm,))
+    sigma = fwhm / (2.0 * math.sqrt(2.0 * math.log(2.0)))
+    R = max(2, int(1.5 * sigma))
+    ax = np.arange(-R, R + 1, dtype=np.float64)
+    r2 = ax[:, None] ** 2 + ax[None, :] ** 2
+    g = np.exp(-r2 / (2.0 * sigma * sigma))
+    fp = (g >= math.exp(-1.5 * 1.5 / 2.0)) | (r2 <= 4.0)
+    npixels = int(fp.sum())
+    gm = g * fp
+    s1 = float(gm.sum())
+    denom = float((gm * gm).sum()) - s1 * s1 / npixels
+    K = ((gm - s1 / npixels) / denom) * fp
+    n = 2 * R + 1
+    # DAOFIND's triangular weights: 1 at the edge of the box, R + 1 in the middle
+    w = R - np.abs(np.arange(n, dtype=np.float64) - R) + 1.0
+    vec = R - np.arange(n, dtype=np.float64)
+    ww = w[:, None] * w[None, :]
+    tables = np.zeros((6, n, n), np.float64)
+    tables[0] = fp
+    tables[1] = ww
+    consts = {}
+    for axis, qg, qd in (('x', 2, 3), ('y', 4, 5)):
+        sg = (g * w[:, None]).sum(axis=0) if axis == 'x' else (g * w[None, :]).sum(axis=1)
+        dg = sg * vec
+        consts[axis] = dict(sumg=float((w * sg).sum()), sumgsq=float((w * sg * sg).sum()), sdgd=float((w * dg).sum()),
+                            sdgds=float((w * dg * dg).sum()), sgdgd=float((w * sg * dg).sum()))
+        tables[qg] = ww * (sg[None, :] if axis == 'x' else sg[:, None])
+        tables[qd] = ww * (dg[None, :] if axis == 'x' else dg[:, None])
+    quad = np.zeros((n, n), np.float64)
+    quad[0:R + 1, R + 1:] = -1.0
+    quad[0:R, 0:R + 1] = 1.0
+    quad[R:, 0:R] = -1.0
+    quad[R + 1:, R:] = 1.0
+    k = dict(fwhm=fwhm, sigma=sigma, R=R, K=K, fp=fp, npixels=npixels, relerr=1.0 / math.sqrt(denom), p=float(w.sum()), consts=consts,
+             tables=tables.reshape(6, n * n), quad=quad)
+    if device is not None:
+        k['dev'] = dict(K=torch.from_numpy(np.ascontiguousarray(K)).to(device),
+                        fp=torch.from_numpy(np.ascontiguousarray(fp.astype(np.uint8))).to(device),
+                        tables=torch.from_numpy(np.ascontiguousarray(k['tables'])).to(device),
+                        quad=torch.from_numpy(np.ascontiguousarray(quad)).to(device))
+    return k
+
+
+def _kernel_on(kernel, device):
+    if 'dev' not in kernel or kernel['dev']['K'].device != device:
+        kernel = dict(kernel)
+        kernel['dev'] = dict(K=torch.from_numpy(np.ascontiguousarray(kernel['K'])).to(device),
+                             fp=torch.from_numpy(np.ascontiguousarray(np.asarray(kernel['fp']).astype(np.uint8))).to(device),
+                             tables=torch.from_numpy(np.ascontiguousarray(kernel['tables'])).to(device),
+                             quad=torch.from_numpy(np.ascontiguousarray(kernel['quad'])).to(device))
+    return kernel
+
+
+def _image_f32(data, name='data'):
+    _need_cuda(data)
+    data = _f32c(data, name)
+    if data.dim() != 2 or data.numel() == 0:
+        raise ValueError('%s must be a non-empty 2-D image, got shape %s' % (name, tuple(data.shape)))
+    return data
+
+
+def daofind_convolve(data, kernel, bg_median=0.0):
+    """float32 image [H, W] -> the image convolved with the DAOFIND kernel (daofind_kernel(fwhm) or a fwhm), float32:
+    d = data - float32(bg_median) inside the image, 0 outside; float64 accumulation over all taps in row-major tap order."""
+    data = _image_f32(data)
+    if not isinstance(kernel, dict):
+        kernel = daofind_kernel(kernel)
+    kernel = _kernel_on(kernel, data.device)
+    out = torch.empty_like(data)
+    check(_lib.load().apgpu_daofind_convolve_f32(_ptr(data), data.shape[0], data.shape[1], _ptr(kernel['dev']['K']), kernel['R'],
+                                                 float(np.float32(bg_median)), _ptr(out), _stream()))
+    return out
+
+
+def local_peaks(values, footprint, threshold, mask=None, border=0, capacity=4096, list_out=None):
+    """Local maxima of a float32 plane under a footprint (2-D bool / uint8 array or tensor; an int n = the n x n square of
+    photutils' find_peaks(box_size=n)): no footprint pixel exceeds the value (outside the image counts as 0), value >
+    threshold (strict), mask == 0, at least `border` pixels from every edge.
+
+    Returns (idx, count): idx = int32 device tensor of flat indices sorted ascending, count = the true number of peaks (python
+    int; one host read).  With count > capacity the list was too short and holds `capacity` of the peaks: call again with
+    capacity=count (find_stars does).  list_out: a caller-owned int32 tensor of at least `capacity` entries to write into."""
+    values = _image_f32(values, 'values')
+    dev = values.device
+    if isinstance(footprint, (int, np.integer)):
+        footprint = np.ones((int(footprint), int(footprint)), np.uint8)
+    if torch.is_tensor(footprint):
+        fp = (footprint != 0).to(device=dev, dtype=torch.uint8).contiguous()
+    else:
+        fp = torch.from_numpy(np.ascontiguousarray((np.asarray(footprint) != 0).astype(np.uint8))).to(dev)
+    if fp.dim() != 2:
+        raise ValueError('footprint must be 2-D')
+    if mask is not None:
+        _need_cuda(mask)
+        if tuple(mask.shape) != tuple(values.shape):
+            raise ValueError('mask must have the image shape')
+        mask = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    capacity = int(capacity)
+    if list_out is None:
+        list_out = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+    elif list_out.dtype != torch.int32 or list_out.numel() < capacity or not list_out.is_contiguous():
+        raise TypeError('list_out must be a contiguous int32 tensor of at least `capacity` entries')
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    check(_lib.load().apgpu_local_peaks_f32(_ptr(values), values.shape[0], values.shape[1], _ptr(fp), fp.shape[0], fp.shape[1],
+                                            float(threshold), _ptr(mask), int(border), _ptr(list_out), capacity, _ptr(count), _stream()))
+    n = int(count.item())
+    idx = torch.sort(list_out[:min(n, capacity)]).values          # order does not depend on scheduling
+    return idx, n
+
+
+def daofind_measure(data, conv, idx, kernel, threshold_eff, bg_median=0.0, sharplo=0.2, sharphi=1.0, roundlo=-1.0, roundhi=1.0):
+    """The DAOFIND quantities of every candidate (int32 flat indices from local_peaks with border = kernel radius).
+    Returns (records float64 [n, 16] in DAOFIND_RECORD order, keep uint8 [n]) as device tensors."""
+    data = _image_f32(data)
+    conv = _image_f32(conv, 'conv')
+    if conv.shape != data.shape:
+        raise ValueError('conv must have the image shape')
+    kernel = _kernel_on(kernel, data.device)
+    idx = idx.to(device=data.device, dtype=torch.int32).contiguous()
+    n = idx.numel()
+    rec = torch.empty((n, len(DAOFIND_RECORD)), dtype=torch.float64, device=data.device)
+    keep = torch.empty(n, dtype=torch.uint8, device=data.device)
+    if n == 0:
+        return rec, keep
+    cx, cy = kernel['consts']['x'], kernel['consts']['y']
+    consts = [kernel['npixels'] - 1.0, float(threshold_eff), sharplo, sharphi, roundlo, roundhi, kernel['sigma'] * kernel['sigma'],
+              kernel['p']]
+    for c in (cx, cy):
+        consts += [c['sumg'], c['sumgsq'], c['sdgd'], c['sdgds'], c['sgdgd']]
+    cd = torch.tensor(consts, dtype=torch.float64).to(data.device)
+    d = kernel['dev']
+    check(_lib.load().apgpu_daofind_measure(_ptr(data), _ptr(conv), data.shape[0], data.shape[1], _ptr(idx), n, kernel['R'],
+                                            float(np.float32(bg_median)), _ptr(d['tables']), _ptr(d['quad']), _ptr(cd), _ptr(rec),
+                                            _ptr(keep), _stream()))
+    return rec, keep
+
+
+def aperture_radii(fwhm):
+    """(aperture radius, annulus inner, annulus outer) of ApFindStars._make_apertures (:272-297)."""
+    import math
+    r = math.ceil(2.0 * float(fwhm))
+    return float(r), float(r), float(math.ceil(1.5 * r))
+
+
+def aperture_photometry(data, xc, yc, fwhm=None, radii=None, sigma=3.0, maxiters=5):
+    """Circular-aperture sums with exact pixel overlaps and the sigma-clipped median of the background annulus
+    (ApFindStars.aperture_photometry, :363-400) for sources at (xc, yc) (x = column; sequences or tensors).
+
+    Returns dict(aperture_sum_raw float64, bkg_median float32, n_annulus int32, area float64, aperture_sum float64 =
+    raw - bkg_median * pi r^2) of device tensors [n]."""
+    import math
+    data = _image_f32(data)
+    dev = data.device
+    r, r_in, r_out = aperture_radii(fwhm) if radii is None else (float(x) for x in radii)
+    xc = torch.as_tensor(xc, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+    yc = torch.as_tensor(yc, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+    if xc.numel() != yc.numel():
+        raise ValueError('xc and yc must have the same length')
+    n = xc.numel()
+    out = dict(aperture_sum_raw=torch.empty(n, dtype=torch.float64, device=dev), bkg_median=torch.empty(n, dtype=torch.float32, device=dev),
+               n_annulus=torch.empty(n, dtype=torch.int32, device=dev), area=torch.empty(n, dtype=torch.float64, device=dev))
+    check(_lib.load().apgpu_aperture_phot_f32(_ptr(data), data.shape[0], data.shape[1], _ptr(xc), _ptr(yc), n, r, r_in, r_out,
+                                              float(sigma), -1 if maxiters is None else int(maxiters), _ptr(out['aperture_sum_raw']),
+                                              _ptr(out['bkg_median']), _ptr(out['n_annulus']), _ptr(out['area']), _stream()))
+    out['aperture_sum'] = out['aperture_sum_raw'] - out['bkg_median'].double() * (math.pi * r * r)
+    return out
+
+
+def find_stars(data, fwhm, threshold, bg_median=0.0, mask=None, capacity=4096):
+    """DAOStarFinder(fwhm, threshold)(data - bg_median, mask) with photutils' defaults (ApFindStars.source_search, :299-340):
+    convolution, peaks, measurement and the rejection rules on the device.  The mask only excludes peaks.
+
+    Returns a dict of device tensors, one entry per kept source ordered by flat pixel index: the DAOFIND_RECORD columns
+    (float64), idx (int32 flat index of the peak), plus n_candidates (python int) and conv (the convolved image).  If the
+    image holds more peaks than `capacity` the peak search is repeated once with a list of the right size."""
+    data = _image_f32(data)
+    kernel = daofind_kernel(fwhm, device=data.device)
+    if kernel['R'] > DAOFIND_MAX_RADIUS:
+        raise ValueError('fwhm = %g needs a kernel radius of %d, the kernels hold %d' % (fwhm, kernel['R'], DAOFIND_MAX_RADIUS))
+    thr_eff = float(threshold) * kernel['relerr']
+    conv = daofind_convolve(data, kernel, bg_median)
+    idx, n = local_peaks(conv, kernel['dev']['fp'], thr_eff, mask=mask, border=kernel['R'], capacity=capacity)
+    if n > capacity:
+        idx, n = local_peaks(conv, kernel['dev']['fp'], thr_eff, mask=mask, border=kernel['R'], capacity=n)
+    rec, keep = daofind_measure(data, conv, idx, kernel, thr_eff, bg_median)
+    sel = keep != 0
+    rec = rec[sel]
+    out = {name: rec[:, c].contiguous() for c, name in enumerate(DAOFIND_RECORD)}
+    out.update(idx=idx[sel], n_candidates=n, conv=conv, threshold_eff=thr_eff, kernel=kernel)
+    return out

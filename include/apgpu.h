@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 #define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form);
-                                       additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes) */
+                                       additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes);
+                                       apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32 */
 
 /* error codes */
 #define APGPU_OK            0
@@ -496,6 +497,50 @@ int apgpu_lacosmic_satmask(const float *data, const uint8_t *inmask, int64_t hei
 int apgpu_lacosmic_iterate(float *clean, const uint8_t *mask, uint8_t *crmask, int64_t height, int64_t width, float sigclip,
                            float sigfrac, float objlim, float readnoise, const float *psfk, float background_level,
                            int64_t *ncr_out, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F6  ApFindStars (core/ApFindStars.py:87-201 the constructor, :299-340 source_search, :363-446 aperture_photometry).
+ *     The reference calls photutils (DAOStarFinder, find_peaks, aperture_photometry), which is not in the build container: the
+ *     entry points implement the published DAOFIND algorithm (Stetson 1987) as restated in tests/findstars_model.py (parity
+ *     with photutils itself is unpinned); the annulus statistic is astropy's sigma_clipped_stats (golden group G16).
+ *     These entry points need no workspace.
+ *
+ *     apgpu_daofind_convolve_f32: out[i][j] = float32( sum_{a,b} kernel[a][b] * d[i + R - a][j + R - b] ), d = data - bg_median
+ *       (one float32 subtraction) inside the image and 0 outside it; kernel [(2R+1)][(2R+1)] float64 on the device (the zero-sum
+ *       DAOFIND kernel, ops.daofind_kernel); all taps in row-major (a, b) order, float64, multiply and add separately
+ *       rounded.  1 <= radius <= 12 (APGPU_EUNSUPPORTED beyond: fwhm too large).
+ *     apgpu_local_peaks_f32: pixel p is a peak when no pixel under the footprint (uint8 [fp_height][fp_width], non-zero = member,
+ *       centred at index size / 2 per axis; a member outside the image holds 0) exceeds values[p], float64(values[p]) >
+ *       threshold (strict), mask[p] == 0 (mask may be NULL) and p lies at least `border` pixels from every image edge.  Peaks go
+ *       into list[capacity] (int32 flat indices, in no particular order: sort them) through a counter: count_out[0] (device
+ *       int32) is ALWAYS the true number of peaks, the list is written only below `capacity` - count_out[0] > capacity tells
+ *       the caller to call again with a larger list.  height * width < 2^31; the footprint is at most 64 x 64.
+ *     apgpu_daofind_measure: per candidate (flat index of a peak at least `radius` from every edge) the DAOFIND quantities from
+ *       the (2R+1)^2 cut-outs of d and of the convolved image: records[n][16] float64 = x_peak, y_peak, npix, peak, conv_peak,
+ *       sharpness, roundness1, roundness2, dx, dy, hx, hy, xcentroid, ycentroid, flux, mag; keep[n] uint8 = 1 where the candidate
+ *       passes the rejection rules (positive fit amplitudes, sharpness / roundness strictly inside their limits, centroid shift
+ *       <= radius, finite values).  tables [6][(2R+1)^2], quad [(2R+1)^2] and consts [18] float64 on the device are the per-tap
+ *       weights and fit constants ops.daofind_kernel builds (consts: npixels - 1, threshold_eff, sharplo, sharphi, roundlo,
+ *       roundhi, sigma^2, p, then sumg, sumgsq, sdgd, sdgds, sgdgd for x and for y).
+ *     apgpu_aperture_phot_f32: per source (xc, yc: float64, x = column) sum_raw = sum overlap * data over the pixels the circle
+ *       of r_aperture touches (exact circle / pixel-square overlap areas, pixel (i, j) covers [j - 0.5, j + 0.5] x [i - 0.5,
+ *       i + 0.5], pixels outside the image contribute nothing), area = the sum of those overlaps, n_annulus = pixels of the
+ *       image whose centre has r_in^2 <= d^2 <= r_out^2, bkg_median = median of astropy's sigma_clipped_stats(annulus values,
+ *       sigma, maxiters) - non-finite values dropped, numpy's float32 arithmetic as apgpu_sigclip_global_f32 - or NaN if none
+ *       is left.  An annulus is held on chip: pi ((r_out + sqrt(1/2))^2 - (r_in - sqrt(1/2))^2) <= 4096 (APGPU_EUNSUPPORTED
+ *       beyond; r_in = 30, r_out = 45 fits).
+ * ------------------------------------------------------------------------------------------- */
+int apgpu_daofind_convolve_f32(const float *data, int64_t height, int64_t width, const double *kernel, int32_t radius,
+                               float bg_median, float *out, void *stream);
+int apgpu_local_peaks_f32(const float *values, int64_t height, int64_t width, const uint8_t *footprint, int32_t fp_height,
+                          int32_t fp_width, double threshold, const uint8_t *mask, int32_t border, int32_t *list,
+                          int32_t capacity, int32_t *count_out, void *stream);
+int apgpu_daofind_measure(const float *data, const float *conv, int64_t height, int64_t width, const int32_t *candidates,
+                          int32_t n_candidates, int32_t radius, float bg_median, const double *tables, const double *quad,
+                          const double *consts, double *records, uint8_t *keep, void *stream);
+int apgpu_aperture_phot_f32(const float *data, int64_t height, int64_t width, const double *xc, const double *yc,
+                            int32_t n_sources, double r_aperture, double r_in, double r_out, double sigma, int32_t maxiters,
+                            double *sum_raw, float *bkg_median, int32_t *n_annulus, double *area, void *stream);
 
 #ifdef __cplusplus
 }
