@@ -22,6 +22,7 @@ _LAZY = {
     'ApFixCosmicRays': ('.core.ApFixCosmicRays', 'ApFixCosmicRays'),
     'ApAutoBadcols': ('.core.ApAutoBadcols', 'ApAutoBadcols'),
     'ApFindStars': ('.core.ApFindStars', 'ApFindStars'),
+    'ApMeasureStars': ('.core.ApMeasureStars', 'ApMeasureStars'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

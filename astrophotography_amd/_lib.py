@@ -19,6 +19,7 @@ CCDPROC_FORM = {'astropy': 0, 'legacy': 1}                                  # AP
 STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_OFFSET: int64 calls, pixels, pixels listed, 64-pixel blocks given up
 
 E_INVAL, E_UNSUPPORTED, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4
+GAUSS2D_REC, GAUSS2D_MAX_BOX = 20, 76                   # APGPU_GAUSS2D_REC, APGPU_GAUSS2D_MAX_BOX
 
 
 class ApGpuError(RuntimeError):
@@ -121,6 +122,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'apgpu_aperture_phot_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double,
                                           C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_gauss2d_fit_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

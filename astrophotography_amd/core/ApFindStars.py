@@ -16,8 +16,9 @@ in the build container, so its published algorithms are restated (tests/findstar
              (apgpu_aperture_phot_f32)
   host    the source tables (a few thousand rows): exposure scaling, magnitudes, sort, trim, files
 
-``_sources`` and ``_phot_table`` are plain dicts of NumPy columns with the reference's column names.  ``measure_fwhm``,
-``plot_image`` and ``write_quality_report`` are not provided (the Gaussian PSF fits of ApMeasureStars and matplotlib).
+``_sources`` and ``_phot_table`` are plain dicts of NumPy columns with the reference's column names.  ``measure_fwhm(None)``
+fits Gaussians to a sample of the stars (core/ApMeasureStars.py, csrc/measurestars.hip) and ``quality_report`` /
+``write_quality_report`` summarise the frame; ``plot_image`` and the plot of the fits are not provided (matplotlib).
 """
 import math
 from datetime import datetime
@@ -347,6 +348,9 @@ class ApFindStars:
             kw_dict['APRX_YHG'] = (imgsiz_y_deg, '[deg] Approximate Y-axis height of image')
             kw_dict['APRX_XPS'] = (3600.0 * pixsiz_x_deg, '[arcseconds] Approximate X-axis plate scale')
             kw_dict['APRX_YPS'] = (3600.0 * pixsiz_y_deg, '[arcseconds] Approximate Y-axis plate scale')
+        if getattr(self, '_fwhm_both', None) is not None:
+            kw_dict['AP_FWHM'] = (self._fwhm_both[0], '[pix] Median FWHM of fitted stars in image')
+            kw_dict['AP_EFWHM'] = (self._fwhm_both[1], '[pix] MAD standard deviation of fitted FWHM')
         kw_dict['AP_BGMED'] = (float(bg_median), '[ADU] Median source-masked background level')
         kw_dict['AP_BGSTD'] = (float(bg_stddev), '[ADU] Std dev of source-masked background level')
         return kw_dict
@@ -362,12 +366,19 @@ class ApFindStars:
         for k, v in self._kw_dict.items():
             pri[k] = v
         pri['HISTORY'] = 'Created by ApFindStars at {}'.format(datetime.now().isoformat(timespec='milliseconds'))
-        fitsio.write_table(str(output_fits_table),
-                           [('AP_XYPOS', {'X': t['xcenter'] + 1.0, 'Y': t['ycenter'] + 1.0}, {'X': 'pix', 'Y': 'pix'},
-                             [('COMMENT', 'Uses FITS 1-based pixel coordinate system.')]),
-                            ('AP_L1MAG', t, {'xcenter': 'pix', 'ycenter': 'pix'},
-                             [('COMMENT', 'Aperature photometry using the DAOFIND kernels of ApFindStars.'),
-                              ('COMMENT', 'Uses python 0-based pixel coordinate system.')])], header=pri)
+        hdus = [('AP_XYPOS', {'X': t['xcenter'] + 1.0, 'Y': t['ycenter'] + 1.0}, {'X': 'pix', 'Y': 'pix'},
+                 [('COMMENT', 'Uses FITS 1-based pixel coordinate system.')]),
+                ('AP_L1MAG', t, {'xcenter': 'pix', 'ycenter': 'pix'},
+                 [('COMMENT', 'Aperature photometry using the DAOFIND kernels of ApFindStars.'),
+                  ('COMMENT', 'Uses python 0-based pixel coordinate system.')])]
+        if getattr(self, '_psf_table', None) is not None:
+            regions = ('CN', 'TL', 'TR', 'BR', 'BL')               # the table writer holds numbers only: region as an index
+            psf = {k: (np.array([regions.index(r) for r in v], np.int32) if k == 'region' else v) for k, v in self._psf_table.items()}
+            hdus.append(('AP_L1PSF', psf, {'xcenter': 'pix', 'ycenter': 'pix'},
+                         [('COMMENT', 'PSF characterization using ApMeasureStars.'),
+                          ('COMMENT', 'Uses python 0-based pixel coordinate system.'),
+                          ('COMMENT', 'region: 0 CN, 1 TL, 2 TR, 3 BR, 4 BL.')]))
+        fitsio.write_table(str(output_fits_table), hdus, header=pri)
 
     def write_ds9_region_file(self, region_file):
         """Write a ds9-format region file (image coordinates, 1-based) with one circle per star of the photometry table."""
@@ -380,12 +391,89 @@ class ApFindStars:
             f_out.write('\n'.join(lines) + '\n')
         self._logger.debug(f'Wrote ds9-format region file to {region_file}')
 
-    # -- out of scope -----------------------------------------------------------------------------------
+    # -- PSF measurement (ApMeasureStars) and the quality report ------------------------------------------
     def measure_fwhm(self, fwhm_plot_file, direction=None):
-        raise NotImplementedError('measure_fwhm needs the Gaussian PSF fits of ApMeasureStars, which are out of scope here.')
+        """Fits 2-D Gaussians to a sample of the stars (ApMeasureStars) and returns (median FWHM, MAD standard deviation,
+        values used) over 'both' axes (default), 'x' or 'y'.  A plot file cannot be written."""
+        if fwhm_plot_file is not None:
+            raise NotImplementedError('measure_fwhm cannot plot the fits (matplotlib is not provided): pass None.')
+        from .ApMeasureStars import ApMeasureStars
+        measure_stars = ApMeasureStars(self._data, self._phot_table, self._search_fwhm, self._bg_median, self._full_srclist, None,
+                                       None, self._loglevel, self._quiet)
+        self._psf_table = measure_stars.results_table()
+        self._nsrcs_fitted = len(self._psf_table['id'])
+        self._fwhm_both = measure_stars.median_fwhm('both')
+        self._fwhm_x = measure_stars.median_fwhm('x')
+        self._fwhm_y = measure_stars.median_fwhm('y')
+        self._logger.info(f'Median FWHM (over x and y) is {self._fwhm_both[0]:.2f} +/- {self._fwhm_both[1]:.2f} pixels '
+                          f'using {self._fwhm_both[2]} data points')
+        if direction is None or direction == 'both':
+            return self._fwhm_both
+        if direction == 'x':
+            return self._fwhm_x
+        if direction == 'y':
+            return self._fwhm_y
+        raise ValueError(f'Unexpected direction={direction} passed to measure_fwhm. Expecting one of None, "both", "x" or "y".')
 
     def plot_image(self, plotfile):
         raise NotImplementedError('plot_image needs matplotlib, which is out of scope here.')
 
+    def quality_report(self):
+        """The reference's quality report (:947-1074) as a dict of dicts: image, background, source, saturation and PSF
+        information.  Null value -999 where there is no plate scale (the reference multiplies by it all the same)."""
+        null_val = -999
+        self._kw_dict = self._build_keyword_dictionary(self._fitsimg, self._hdr, self._bg_median, self._bg_stddev)
+        kw = self._kw_dict
+        im_info = {}
+        for okey, fkw in (('file', 'IMG_FILE'), ('ncols', 'IMG_COLS'), ('nrows', 'IMG_ROWS'), ('object', 'OBJECT'),
+                          ('telescope', 'TELESCOP'), ('filter', 'FILTER'), ('date-obs', 'DATE-OBS'), ('exposure', 'EXPOSURE'),
+                          ('ccd_temperature', 'CCD-TEMP'), ('electronic_gain', 'EGAIN'), ('airmass', 'AIRMASS'),
+                          ('approx_width_deg', 'APRX_XWD'), ('approx_height_deg', 'APRX_YHG'), ('approx_xpixsiz_arcs', 'APRX_XPS'),
+                          ('approx_ypixsiz_arcs', 'APRX_YPS')):
+            if fkw in kw:
+                v = kw[fkw][0]
+                im_info[okey] = v.item() if isinstance(v, np.generic) else v
+            else:
+                self._logger.warning(f'Keyword {fkw} not found, not written to quality report.')
+        bg_info = {'median': kw['AP_BGMED'][0], 'stddev': kw['AP_BGSTD'][0]}
+        stats = self._phot_stats if getattr(self, '_phot_stats', None) else ((null_val, 0),) * 3
+        src_info = {'num_detected': int(kw['AP_NDET'][0]), 'num_with_photometry': int(kw['AP_NPHOT'][0]),
+                    'search_nsigma': kw['AP_NSIGM'][0], 'adups_brightest': stats[0][0], 'adups_median': stats[1][0],
+                    'adups_faintest': stats[2][0]}
+        sat_info = {'num_saturated_in_image': int(self._nsrcs_saturated),
+                    'num_saturated_in_photometry': int(np.sum(np.asarray(self._phot_table['psbl_sat']) == True))}   # noqa: E712
+        psf_info = {'num_fit': int(kw['AP_NFIT'][0])}
+        have_platescale = 'APRX_XPS' in kw and 'APRX_YPS' in kw
+        if not have_platescale:
+            self._logger.warning('Skipping some quality reporting that requires an estimate platescale.')
+        if self._psf_table is not None:
+            if have_platescale:
+                xps, yps = kw['APRX_XPS'][0], kw['APRX_YPS'][0]
+                avg = math.sqrt(0.5 * (xps ** 2 + yps ** 2))
+            else:
+                xps = yps = avg = null_val
+            from .ApMeasureStars import ApMeasureStars
+            psf_info['circular_psf'] = ApMeasureStars.is_circular(self._fwhm_x[0], self._fwhm_y[0], self._fwhm_x[1], self._fwhm_y[1])
+            for name, result, pix in (('fwhm_xandy', self._fwhm_both, avg), ('fwhm_x', self._fwhm_x, xps), ('fwhm_y', self._fwhm_y, yps)):
+                psf_info[name] = {'fwhm_val_pix': float(result[0]), 'fwhm_err_pix': float(result[1]),
+                                  'fwhm_val_arcs': float(result[0] * pix), 'fwhm_err_arcs': float(result[1] * pix),
+                                  'num_data_pts': int(result[2])}
+        return {'image_info': im_info, 'background_info': bg_info, 'source_info': src_info, 'saturation_info': sat_info,
+                'psf_info': psf_info}
+
     def write_quality_report(self, quality_report_name):
-        raise NotImplementedError('write_quality_report summarises the FWHM fits of ApMeasureStars, which are out of scope here.')
+        """Writes quality_report() as YAML (floats with six decimals, as the reference's representer)."""
+        if getattr(self, '_psf_table', None) is None:
+            raise NotImplementedError('write_quality_report summarises the FWHM fits: call measure_fwhm(None) first.')
+        try:
+            import yaml
+        except ImportError as exc:                                               # pragma: no cover
+            raise RuntimeError('write_quality_report needs PyYAML') from exc
+
+        class _Dumper(yaml.SafeDumper):
+            pass
+
+        _Dumper.add_representer(float, lambda dumper, value: dumper.represent_scalar('tag:yaml.org,2002:float', '{0:.6f}'.format(value)))
+        with open(quality_report_name, 'w') as write_file:
+            yaml.dump(self.quality_report(), write_file, Dumper=_Dumper, indent=4, sort_keys=False)
+        self._logger.info(f'Wrote image quality report to {quality_report_name}')

@@ -1414,3 +1414,73 @@ def find_stars(data, fwhm, threshold, bg_median=0.0, mask=None, capacity=4096):
     out = {name: rec[:, c].contiguous() for c, name in enumerate(DAOFIND_RECORD)}
     out.update(idx=idx[sel], n_candidates=n, conv=conv, threshold_eff=thr_eff, kernel=kernel)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F7: ApMeasureStars - Gaussian PSF fits (csrc/measurestars.hip)
+SIGMA_TO_FWHM = 2.35482                                     # the reference's constant (ApMeasureStars.py:245)
+GAUSS2D_COLUMNS = ('xc_fit', 'xc_err', 'yc_fit', 'yc_err', 'ampl', 'ampl_err', 'fwhm_x', 'fwhm_x_err', 'fwhm_y', 'fwhm_y_err', 'theta',
+                   'theta_err', 'axrat', 'axrat_err', 'circular', 'fit_ok', 'rchisq')
+
+
+def fit_box_width(init_fwhm):
+    """(box width, edge exclusion) of ApMeasureStars._fit_box_initialization (:526-534)."""
+    import math
+    box = max(2 * int(3.0 * init_fwhm), 12)
+    return box, 2 * int(math.ceil(box / 4))
+
+
+def gauss2d_fit(data, xcenter, ycenter, peak, bg, init_fwhm, box_width=None, max_iter=500):
+    """The three-stage 2-D Gaussian + constant fits of ApMeasureStars._do_fitting (:223-430) for stars at (xcenter, ycenter)
+    (x = column) with starting amplitudes `peak` and background levels `bg` (sequences, or one number for bg), one wavefront per
+    star.  The box of a star is [rint(centre) - box_width / 2, + box_width / 2) per axis and must lie inside the image.
+
+    Returns a dict of float64 NumPy columns named as the reference's table (GAUSS2D_COLUMNS; circular and fit_ok are bool) plus
+    bg_fit, niter [n, 3] (int64) and xmin / xmax / ymin / ymax.  The reference's axes are kept: the model's x runs along the
+    ROWS of the cut-out, yet xc_fit = x_mean + xmin.  Error columns, axrat_err and circular (True) stay at their defaults where
+    fit_ok is False."""
+    import math
+    import numpy as np
+    data = _image_f32(data)
+    dev = data.device
+    H, W = int(data.shape[0]), int(data.shape[1])
+    xcenter = np.atleast_1d(np.asarray(xcenter, np.float64)).reshape(-1)
+    ycenter = np.atleast_1d(np.asarray(ycenter, np.float64)).reshape(-1)
+    n = xcenter.size
+    peak = np.broadcast_to(np.asarray(peak, np.float64).reshape(-1), (n,)) if n else np.zeros(0)
+    bg = np.broadcast_to(np.asarray(bg, np.float64).reshape(-1), (n,)) if n else np.zeros(0)
+    if ycenter.size != n:
+        raise ValueError('xcenter and ycenter must have the same length')
+    Wb = fit_box_width(init_fwhm)[0] if box_width is None else int(box_width)
+    half = Wb / 2
+    nx, ny = np.rint(xcenter).astype(np.int64), np.rint(ycenter).astype(np.int64)
+    out = {'xmin': nx - half, 'xmax': nx + half, 'ymin': ny - half, 'ymax': ny + half}
+    if n and Wb % 2 == 0 and (out['xmin'].min() < 0 or out['ymin'].min() < 0 or out['xmax'].max() > W or out['ymax'].max() > H):
+        raise ValueError('gauss2d_fit: a %d-pixel fit box lies outside the [%d, %d] image' % (Wb, H, W))
+    sig_y = float(init_fwhm) * (1.0 / SIGMA_TO_FWHM)
+    init = np.empty((n, 7))
+    init[:, 0], init[:, 1], init[:, 2], init[:, 3], init[:, 4] = peak, 1.05 * sig_y, sig_y, 1.1, bg
+    init[:, 5], init[:, 6] = xcenter - out['xmin'], ycenter - out['ymin']
+    box_y = torch.from_numpy(out['ymin'].astype(np.int32)).to(dev)
+    box_x = torch.from_numpy(out['xmin'].astype(np.int32)).to(dev)
+    init_t = torch.from_numpy(init).to(dev).contiguous()
+    rec_t = torch.zeros((n, _lib.GAUSS2D_REC), dtype=torch.float64, device=dev)
+    ok_t = torch.zeros(n, dtype=torch.int32, device=dev)
+    check(_lib.load().apgpu_gauss2d_fit_f32(_ptr(data), H, W, _ptr(box_y), _ptr(box_x), _ptr(init_t), n, Wb, int(max_iter), _ptr(rec_t),
+                                            _ptr(ok_t), _stream()))
+    rec, okf = rec_t.cpu().numpy(), ok_t.cpu().numpy()
+    if (okf < 0).any():
+        raise ValueError('gauss2d_fit: a fit box lies outside the image')
+    ok = okf == 1
+    fx, fy = SIGMA_TO_FWHM * rec[:, 1], SIGMA_TO_FWHM * rec[:, 2]
+    fxe, fye = np.where(ok, SIGMA_TO_FWHM * rec[:, 8], 0.0), np.where(ok, SIGMA_TO_FWHM * rec[:, 9], 0.0)
+    with np.errstate(all='ignore'):
+        axrat = np.maximum(fx, fy) / np.minimum(fx, fy)
+        axrat_err = np.where(ok, axrat * np.sqrt((fxe / fx) ** 2 + (fye / fy) ** 2), 0.0)
+        circular = ~(ok & (np.abs(fy - fx) / fye > 3.0))                  # is_circular (:433-445): fwhm_yerr only
+    out.update(xc_fit=rec[:, 5] + out['xmin'], xc_err=np.where(ok, rec[:, 12], 0.0), yc_fit=rec[:, 6] + out['ymin'],
+               yc_err=np.where(ok, rec[:, 13], 0.0), ampl=rec[:, 0].copy(), ampl_err=np.where(ok, rec[:, 7], 0.0), fwhm_x=fx,
+               fwhm_x_err=fxe, fwhm_y=fy, fwhm_y_err=fye, theta=rec[:, 3].copy(), theta_err=np.where(ok, rec[:, 10], 0.0), axrat=axrat,
+               axrat_err=axrat_err, circular=circular, fit_ok=ok, rchisq=rec[:, 14].copy(), bg_fit=rec[:, 4].copy(),
+               bg_err=np.where(ok, rec[:, 11], 0.0), niter=rec[:, 16:19].astype(np.int64))
+    return out

@@ -2,9 +2,10 @@
 """ap_find_stars - detect the stars of a FITS image and write their positions and aperture photometry to a FITS table
 (reference: scripts/ap_find_stars.py).
 
-Deviation: the script does ONE source search, at --search_fwhm.  The reference fits Gaussians to a sample of the stars
-(ApMeasureStars) and searches again with the measured FWHM; those fits, the plots and the quality report are not
-provided: --plotfile, --quality_report and --fwhm_plot are accepted and a warning says that nothing is written."""
+By default the script does ONE source search, at --search_fwhm.  With --fit_fwhm (implied by --quality_report) it follows the
+reference: Gaussians are fitted to a sample of the stars (ApMeasureStars), the search and the photometry are repeated at the
+measured FWHM, and the quality report is written.  The plots are not provided: --plotfile and --fwhm_plot are accepted and a
+warning says that nothing is written."""
 import argparse
 import logging
 
@@ -13,7 +14,8 @@ def command_line_opts(argv):
     parser = argparse.ArgumentParser(prog='ap_find_stars',
                                      description=('Detects stars within a FITS image and performs aperture photometry on them, '
                                                   'writing the source list to a FITS table. One search is made, at '
-                                                  '--search_fwhm: the FWHM is not fitted and the search is not repeated.'))
+                                                  '--search_fwhm, unless --fit_fwhm or --quality_report asks for the FWHM to be '
+                                                  'fitted and the search to be repeated at the measured value.'))
     parser.add_argument('fits_image', metavar='IN_IMAGE.FITS', help='Path/name of the FITS image to search for stars.')
     parser.add_argument('source_list', metavar='OUT_SRCLIST.FITS', help='Path/name of the output FITS table of sources.')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
@@ -40,7 +42,11 @@ def command_line_opts(argv):
                               'width 8x search_fwhm centered on possibly saturated stars are excluded from source detection '
                               'and fitting.'))
     parser.add_argument('--plotfile', default=None, metavar='IMG_WITH_SRCS.PNG', help='Accepted; no plot is produced.')
-    parser.add_argument('--quality_report', default=None, metavar='QUALITY_REPORT.TXT', help='Accepted; no report is produced.')
+    parser.add_argument('--fit_fwhm', action='store_true', default=False,
+                        help=('Fit 2-D Gaussians to a sample of the stars, then repeat the search and the photometry at the '
+                              'measured FWHM.'))
+    parser.add_argument('--quality_report', default=None, metavar='QUALITY_REPORT.TXT',
+                        help='Name for the optional YAML image quality report (seeing, PSF circularity). Implies --fit_fwhm.')
     parser.add_argument('--fwhm_plot', default=None, metavar='FWHM_FITS.PNG', help='Accepted; no plot is produced.')
     parser.add_argument('-d', '--ds9', default=None, metavar='ds9.reg', help='Name for optional ds9-format region file.')
     parser.add_argument('-q', '--quiet', action='store_true', default=False,
@@ -52,14 +58,27 @@ def main(args=None):
     p_args = command_line_opts(args)
     import astrophotography_amd as ap
     log = logging.getLogger('ap_find_stars')
-    for flag, val in (('--plotfile', p_args.plotfile), ('--quality_report', p_args.quality_report), ('--fwhm_plot', p_args.fwhm_plot)):
+    for flag, val in (('--plotfile', p_args.plotfile), ('--fwhm_plot', p_args.fwhm_plot)):
         if val is not None:
-            log.warning('%s %s: not produced (plots, the quality report and the FWHM fits are not provided).', flag, val)
+            log.warning('%s %s: not produced (plots are not provided).', flag, val)
     find_stars = ap.ApFindStars(p_args.fits_image, p_args.fits_extension, p_args.search_fwhm, p_args.search_nsigma, p_args.bitdepth,
                                 p_args.max_sources, p_args.retain_saturated, p_args.sat_frac, p_args.loglevel, None, p_args.quiet)
+    if p_args.fit_fwhm or p_args.quality_report is not None:
+        new_fwhm, _, num_used = find_stars.measure_fwhm(None)
+        if not num_used or not new_fwhm > 0:
+            raise RuntimeError('No star could be fitted: the FWHM was not measured.')
+        from astrophotography_amd import ops
+        radius = ops.daofind_kernel(new_fwhm)['R']
+        if radius > ops.DAOFIND_MAX_RADIUS:
+            raise RuntimeError(f'The measured FWHM of {new_fwhm:.2f} pixels needs a search kernel of radius {radius}, above the '
+                               f'star finder\'s limit of {ops.DAOFIND_MAX_RADIUS}.')
+        find_stars.source_search(new_fwhm, p_args.search_nsigma)
+        find_stars.aperture_photometry()
     if p_args.ds9 is not None:
         find_stars.write_ds9_region_file(p_args.ds9)
     find_stars.write_source_list(p_args.source_list)
+    if p_args.quality_report is not None:
+        find_stars.write_quality_report(p_args.quality_report)
     return 0
 
 

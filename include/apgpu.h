@@ -32,7 +32,8 @@ extern "C" {
 
 #define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form);
                                        additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes);
-                                       apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32 */
+                                       apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32;
+                                       apgpu_gauss2d_fit_f32 */
 
 /* error codes */
 #define APGPU_OK            0
@@ -541,6 +542,37 @@ int apgpu_daofind_measure(const float *data, const float *conv, int64_t height, 
 int apgpu_aperture_phot_f32(const float *data, int64_t height, int64_t width, const double *xc, const double *yc,
                             int32_t n_sources, double r_aperture, double r_in, double r_out, double sigma, int32_t maxiters,
                             double *sum_raw, float *bkg_median, int32_t *n_annulus, double *area, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F7  ApMeasureStars (core/ApMeasureStars.py:223-430): weighted least-squares fits of A exp(-(a du^2 + b du dv + c dv^2)) + B
+ *     (astropy's Gaussian2D + Const2D; a, b, c from x_stddev, y_stddev, theta) to n square cut-outs of a float32 image, one
+ *     wavefront per star, float64.  The cut-out of star s is img[box_y[s] .. + box_width)[box_x[s] .. + box_width); u is the
+ *     ROW index and v the column index inside it (np.mgrid: the reference's axes, kept).  Weights 1 / sd with v = d > 0 ? d : 1,
+ *     sd = v != 1 ? sqrt(v) : sqrt(mean of the v != 1), in the reference's float32 arithmetic; no v != 1 at all: not fitted.
+ *     init [n][7] and the first 7 entries of a record are A, x_stddev, y_stddev, theta, B, x_mean, y_mean (APGPU_GAUSS2D_*).
+ *     Levenberg-Marquardt with the analytic Jacobian in the reference's three stages (4, 5, 7 leading parameters free; a stage
+ *     runs if the one before converged; at most max_iter iterations each; a stage ends when every step is <= 1e-10 of its
+ *     parameter, or of the parameter's unit-weight error if that is larger).
+ *     out_rec [n][APGPU_GAUSS2D_REC] float64: the parameters [0..7), their standard errors [7..14) (sqrt(diag((J^T W J)^-1)
+ *     chi^2 / (box_width - n_free)): astropy's scaling, whose degrees of freedom count the ROWS of the 2-D grid; 0 for
+ *     parameters not free in the last converged stage and when the fit is not ok), [14] chi^2 / (box_width^2 - n_free),
+ *     [15] chi^2, [16..19) iterations per stage, [19] n_free of the last stage run.  out_ok [n] int32: 1 all three stages
+ *     converged with a positive-definite matrix, 0 not, -1 the box does not lie inside the image (nothing read).
+ *     box_width even, 12 .. APGPU_GAUSS2D_MAX_BOX (APGPU_EUNSUPPORTED above: the cut-out is held in LDS).
+ *     All pointers but img's shape arguments are device pointers.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_GAUSS2D_REC 20
+#define APGPU_GAUSS2D_MAX_BOX 76
+#define APGPU_GAUSS2D_AMPL 0
+#define APGPU_GAUSS2D_XSTD 1
+#define APGPU_GAUSS2D_YSTD 2
+#define APGPU_GAUSS2D_THETA 3
+#define APGPU_GAUSS2D_BG 4
+#define APGPU_GAUSS2D_XMEAN 5
+#define APGPU_GAUSS2D_YMEAN 6
+int apgpu_gauss2d_fit_f32(const float *img, int64_t height, int64_t width, const int32_t *box_y, const int32_t *box_x,
+                          const double *init, int32_t n, int32_t box_width, int32_t max_iter, double *out_rec, int32_t *out_ok,
+                          void *stream);
 
 #ifdef __cplusplus
 }
