@@ -23,6 +23,7 @@ _LAZY = {
     'ApAutoBadcols': ('.core.ApAutoBadcols', 'ApAutoBadcols'),
     'ApFindStars': ('.core.ApFindStars', 'ApFindStars'),
     'ApMeasureStars': ('.core.ApMeasureStars', 'ApMeasureStars'),
+    'ApRegister': ('.core.ApRegister', 'ApRegister'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

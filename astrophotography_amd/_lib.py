@@ -20,6 +20,7 @@ STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_O
 
 E_INVAL, E_UNSUPPORTED, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4
 GAUSS2D_REC, GAUSS2D_MAX_BOX = 20, 76                   # APGPU_GAUSS2D_REC, APGPU_GAUSS2D_MAX_BOX
+REGISTER_MAX_K, REGISTER_MAX_STARS = 64, 4096           # APGPU_REGISTER_MAX_K, APGPU_REGISTER_MAX_STARS
 
 
 class ApGpuError(RuntimeError):
@@ -124,6 +125,12 @@ SIGNATURES = {
                                           C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'apgpu_gauss2d_fit_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_triangle_build': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_triangle_vote': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                      C.c_void_p, C.c_void_p]),
+    'apgpu_nearest_match': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

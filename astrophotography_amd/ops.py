@@ -1484,3 +1484,187 @@ def gauss2d_fit(data, xcenter, ycenter, peak, bg, init_fwhm, box_width=None, max
                axrat_err=axrat_err, circular=circular, fit_ok=ok, rchisq=rec[:, 14].copy(), bg_fit=rec[:, 4].copy(),
                bg_err=np.where(ok, rec[:, 11], 0.0), niter=rec[:, 16:19].astype(np.int64))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F8: ApRegister - star-list registration by triangle similarity (csrc/register.hip)
+REGISTER_IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _star_lists(xy, count):
+    xy = torch.as_tensor(xy, dtype=torch.float64)
+    if xy.dim() != 3 or xy.shape[2] != 2 or xy.shape[1] < 1:
+        raise ValueError('xy must be [frames, stars >= 1, 2], got %s' % (tuple(xy.shape),))
+    count = torch.as_tensor(count, dtype=torch.int32).reshape(-1)
+    if count.numel() != xy.shape[0]:
+        raise ValueError('count must hold one entry per frame')
+    dev = xy.device if xy.is_cuda else torch.device('cuda')
+    return xy.to(dev).contiguous(), count.to(dev).contiguous()
+
+
+def triangle_build(xy, count, K=40, min_side=5.0):
+    """The similarity invariants of every triangle among the K brightest stars of each list (xy [F, M, 2] float64, x = column,
+    brightest first; count [F]).  A triangle is kept iff its shortest side is >= min_side, y >= 0.1, x <= 0.98 and y <= 0.98 x.
+
+    Returns dict(xy float64 [F, T, 2] = (sqrt(b2 / a2), sqrt(c2 / a2)), v int32 [F, T] = v0 | v1 << 8 | v2 << 16 | (orientation
+    + 1) << 24, count int32 [F], K) of device tensors, T = K (K-1) (K-2) / 6; a frame's list is in no particular order
+    (triangle_unpack sorts it)."""
+    K = int(K)
+    if not 3 <= K <= _lib.REGISTER_MAX_K:
+        raise ValueError('K = %d is outside 3 .. %d' % (K, _lib.REGISTER_MAX_K))
+    xy, count = _star_lists(xy, count)
+    F, M = int(xy.shape[0]), int(xy.shape[1])
+    T = K * (K - 1) * (K - 2) // 6
+    out = dict(xy=torch.empty((F, T, 2), dtype=torch.float64, device=xy.device), v=torch.empty((F, T), dtype=torch.int32, device=xy.device),
+               count=torch.empty(F, dtype=torch.int32, device=xy.device), K=K)
+    check(_lib.load().apgpu_triangle_build(_ptr(xy), _ptr(count), F, M, K, float(min_side), T, _ptr(out['xy']), _ptr(out['v']),
+                                           _ptr(out['count']), _stream()))
+    return out
+
+
+def triangle_unpack(tri):
+    """triangle_build's lists on the host: per frame a dict(x, y float64 [n]; v int64 [n, 3] = v0, v1, v2; orient int64 [n]),
+    sorted by (v0, v1, v2)."""
+    xy, v, n = tri['xy'].cpu().numpy(), tri['v'].cpu().numpy().astype(np.int64), tri['count'].cpu().numpy()
+    frames = []
+    for f in range(len(n)):
+        w = v[f, :n[f]]
+        vv = np.stack([w & 0xff, (w >> 8) & 0xff, (w >> 16) & 0xff], axis=1)
+        order = np.lexsort((vv[:, 2], vv[:, 1], vv[:, 0]))
+        frames.append(dict(x=xy[f, :n[f], 0][order], y=xy[f, :n[f], 1][order], v=vv[order], orient=((w >> 24) - 1)[order]))
+    return frames
+
+
+def triangle_vote(tri, eps=0.002, allow_mirror=False):
+    """votes int32 [F, K, K] (device): votes[f, i, j] = the matching (reference triangle, frame-f triangle) pairs - invariants
+    within eps of each other, inclusive, and equal orientation unless allow_mirror - in which reference star i and star j of
+    frame f are the same canonical vertex.  Exact integers, the same on every run."""
+    F, T = int(tri['v'].shape[0]), int(tri['v'].shape[1])
+    K = int(tri['K'])
+    votes = torch.empty((F, K, K), dtype=torch.int32, device=tri['v'].device)
+    check(_lib.load().apgpu_triangle_vote(_ptr(tri['xy']), _ptr(tri['v']), _ptr(tri['count']), F, T, K, float(eps), int(bool(allow_mirror)),
+                                          _ptr(votes), _stream()))
+    return votes
+
+
+def nearest_match(xy, count, transforms, radius):
+    """Nearest neighbours under per-frame affines (transforms [F, 6], reference -> frame): fwd_idx / fwd_d2 [F, M] for every
+    reference star the nearest star of frame f to its image and the squared distance, bwd_idx / bwd_d2 [F, M] for every star of
+    frame f the reference star whose image is nearest.  Only neighbours with d2 <= radius^2 (inclusive) count; ties go to the
+    lower index; no neighbour: -1 and inf.  Device tensors."""
+    xy, count = _star_lists(xy, count)
+    F, M = int(xy.shape[0]), int(xy.shape[1])
+    if M > _lib.REGISTER_MAX_STARS:
+        raise ValueError('lists of %d stars: at most %d' % (M, _lib.REGISTER_MAX_STARS))
+    T = torch.as_tensor(np.asarray(transforms, np.float64).reshape(F, 6)).to(xy.device).contiguous()
+    idx = torch.empty((2, F, M), dtype=torch.int32, device=xy.device)
+    d2 = torch.empty((2, F, M), dtype=torch.float64, device=xy.device)
+    check(_lib.load().apgpu_nearest_match(_ptr(xy), _ptr(count), _ptr(T), F, M, float(radius), _ptr(idx[0]), _ptr(d2[0]), _ptr(idx[1]),
+                                          _ptr(d2[1]), _stream()))
+    return dict(fwd_idx=idx[0], fwd_d2=d2[0], bwd_idx=idx[1], bwd_d2=d2[1])
+
+
+def _register_apply(A, pts):
+    return np.stack([(A[0] * pts[:, 0] + A[1] * pts[:, 1]) + A[2], (A[3] * pts[:, 0] + A[4] * pts[:, 1]) + A[5]], axis=1)
+
+
+def _register_fit(r, s, kind):
+    """Least squares s ~ T(r), coordinates centred on r's mean: 'similarity' (4 parameters), 'mirror' (a similarity after a
+    reflection) or 'affine' (6).  Returns (coefficients [6], 2-D rms of the residuals)."""
+    m = r.mean(axis=0)
+    xc, yc = r[:, 0] - m[0], r[:, 1] - m[1]
+    one, zero = np.ones_like(xc), np.zeros_like(xc)
+    if kind == 'affine':
+        D = np.stack([xc, yc, one], axis=1)
+        (a0, a1, tx), (a3, a4, ty) = np.linalg.lstsq(D, s[:, 0], rcond=None)[0], np.linalg.lstsq(D, s[:, 1], rcond=None)[0]
+    else:
+        sgn = 1.0 if kind == 'similarity' else -1.0
+        D = np.concatenate([np.stack([xc, -sgn * yc, one, zero], axis=1), np.stack([sgn * yc, xc, zero, one], axis=1)])
+        a, b, tx, ty = np.linalg.lstsq(D, np.concatenate([s[:, 0], s[:, 1]]), rcond=None)[0]
+        a0, a1, a3, a4 = a, -sgn * b, b, sgn * a
+    A = np.array([a0, a1, tx - (a0 * m[0] + a1 * m[1]), a3, a4, ty - (a3 * m[0] + a4 * m[1])])
+    res = _register_apply(A, r) - s
+    return A, float(np.sqrt(np.mean(res[:, 0] ** 2 + res[:, 1] ** 2)))
+
+
+def _register_seeds(V):
+    """Mutual arg-max pairs (lowest index on ties) of one frame's votes [K, K] that hold at least half the largest vote."""
+    vmax = int(V.max()) if V.size else 0
+    if vmax <= 0:
+        return np.zeros((0, 2), np.int64)
+    row_best, col_best = V.argmax(axis=1), V.argmax(axis=0)
+    i = np.arange(V.shape[0])
+    ok = (col_best[row_best] == i) & (V[i, row_best] > 0) & (2 * V[i, row_best].astype(np.int64) >= vmax)
+    return np.stack([i[ok], row_best[ok]], axis=1).astype(np.int64)
+
+
+def register_lists(xy, count, K=40, eps=0.002, min_side=5.0, match_radius=3.0, model='affine', allow_mirror=False, max_rounds=4):
+    """Registers frames 1 .. F-1 on frame 0 from their star lists (xy [F, M, 2] float64, x = column, 0-based pixel centres,
+    brightest first, padded; count [F]): triangle votes among the K brightest stars -> seed pairs -> a similarity fit -> up to
+    max_rounds rounds of (mutual nearest neighbours on the full lists, refit with `model`: 'affine' from 6 pairs on, else a
+    similarity).  The rule is DESIGN 4.3e; the kernels do the triangle and neighbour searches, the fits are a few float64
+    NumPy lines.
+
+    Returns a dict over frames: coeffs [F, 6] (x_frame = a0 x + a1 y + a2, y_frame = a3 x + a4 y + a5 for x, y on the grid of
+    frame 0: what resample_affine and ap_coadd take; NaN where not ok), ok [F] bool, n_seed, n_matched [F], rms [F] (the 2-D
+    rms of the matched pairs about the fit, pixels), pairs (per frame [n, 2]: reference index, frame index) and votes (device).
+    A frame that cannot be registered has ok = False: that is a status, not an error.  Frame 0 gets the identity."""
+    if model not in ('affine', 'similarity'):
+        raise ValueError("model must be 'affine' or 'similarity', got %r" % (model,))
+    xy, count = _star_lists(xy, count)
+    F, M = int(xy.shape[0]), int(xy.shape[1])
+    tri = triangle_build(xy, count, K, min_side)
+    votes_t = triangle_vote(tri, eps, allow_mirror)
+    votes = votes_t.cpu().numpy()
+    pts, cnt = xy.cpu().numpy(), np.clip(count.cpu().numpy(), 0, M)
+    out = dict(coeffs=np.full((F, 6), np.nan), ok=np.zeros(F, bool), n_seed=np.zeros(F, np.int64), n_matched=np.zeros(F, np.int64),
+               rms=np.full(F, np.nan), pairs=[np.zeros((0, 2), np.int64) for _ in range(F)], votes=votes_t)
+    out['coeffs'][0], out['ok'][0], out['rms'][0], out['n_matched'][0] = REGISTER_IDENTITY, True, 0.0, cnt[0]
+    out['pairs'][0] = np.stack([np.arange(cnt[0]), np.arange(cnt[0])], axis=1)
+    A = np.tile(np.asarray(REGISTER_IDENTITY), (F, 1))
+    rms, kind, seeds, pairs = np.zeros(F), ['similarity'] * F, [None] * F, [None] * F
+    live = []
+    for f in range(1, F):
+        seeds[f] = _register_seeds(votes[f])
+        out['n_seed'][f] = len(seeds[f])
+        if len(seeds[f]) < 3:
+            continue
+        r, s = pts[0, seeds[f][:, 0]], pts[f, seeds[f][:, 1]]
+        A[f], rms[f] = _register_fit(r, s, 'similarity')
+        if allow_mirror:
+            Am, rmsm = _register_fit(r, s, 'mirror')
+            if rmsm < rms[f]:
+                A[f], rms[f], kind[f] = Am, rmsm, 'mirror'
+        live.append(f)
+    for rnd in range(max_rounds):
+        if not live:
+            break
+        # one launch per radius: in the first round all frames share match_radius, later each has its own
+        radius = {f: float(match_radius) if rnd == 0 else float(np.clip(3.0 * rms[f], 0.5, match_radius)) for f in live}
+        found = {}
+        for rad in sorted(set(radius.values())):
+            nm = nearest_match(xy, count, A, rad)
+            fwd, bwd = nm['fwd_idx'].cpu().numpy(), nm['bwd_idx'].cpu().numpy()
+            for f in live:
+                if radius[f] == rad:
+                    i = np.nonzero(fwd[f] >= 0)[0]
+                    i = i[bwd[f][fwd[f][i]] == i]
+                    found[f] = np.stack([i, fwd[f][i]], axis=1).astype(np.int64)
+        still = []
+        for f in live:
+            if pairs[f] is not None and np.array_equal(found[f], pairs[f]):
+                continue
+            pairs[f] = found[f]
+            if len(pairs[f]) < 3:
+                continue
+            A[f], rms[f] = _register_fit(pts[0, pairs[f][:, 0]], pts[f, pairs[f][:, 1]],
+                                         'affine' if model == 'affine' and len(pairs[f]) >= 6 else kind[f])
+            still.append(f)
+        live = still
+    for f in range(1, F):
+        if pairs[f] is None:
+            continue
+        out['n_matched'][f], out['pairs'][f] = len(pairs[f]), pairs[f]
+        if len(pairs[f]) >= max(3, len(seeds[f])):
+            out['coeffs'][f], out['ok'][f], out['rms'][f] = A[f], True, rms[f]
+    return out

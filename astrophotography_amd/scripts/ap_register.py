@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""ap_register - register dithered frames on a reference frame from their stars and write the transforms file of ap_coadd:
+
+    ap_register -o transforms.yml frame-0001.fits frame-0002.fits frame-0003.fits
+    ap_coadd coadd.fits frame-0001.fits frame-0002.fits frame-0003.fits --transforms transforms.yml
+
+The first input is the reference.  An input is either an image (its stars are found with ApFindStars) or a source list written
+by ap_find_stars (a FITS file with an AP_L1MAG extension; its frame is named after the list's IMG_FILE card).  The stars of
+the lists are matched by triangle similarity and one affine per frame is fitted (ApRegister)."""
+import argparse
+import logging
+
+
+def command_line_opts(argv):
+    parser = argparse.ArgumentParser(prog='ap_register', description='Register frames on a reference frame from their star lists.')
+    parser.add_argument('reference', metavar='REF', help='Reference image or source list.')
+    parser.add_argument('sources', metavar='SRC', nargs='*', help='Images or source lists to register on the reference.')
+    parser.add_argument('-o', '--output', required=True, metavar='TRANSFORMS.YML', help='Output transforms file (overwritten).')
+    parser.add_argument('-K', '--nbright', default=40, type=int, metavar='K',
+                        help='Triangles are built from the K brightest stars of each list (3 .. 64). Default: 40')
+    parser.add_argument('--eps', default=0.002, type=float, help='Tolerance on the triangle invariants. Default: 0.002')
+    parser.add_argument('--match_radius', default=3.0, type=float, metavar='PIXELS', help='Largest match distance. Default: 3.0')
+    parser.add_argument('--model', default='affine', choices=['affine', 'similarity'], help='Fitted transform. Default: affine')
+    parser.add_argument('--allow_mirror', action='store_true', help='Also match a mirrored frame.')
+    parser.add_argument('--skip_failed', action='store_true',
+                        help='Leave frames that cannot be registered out of the output, with a warning. Default: an error.')
+    parser.add_argument('--search_fwhm', default=3.0, type=float, help='Source search FWHM for images (pixels). Default: 3.0')
+    parser.add_argument('--search_nsigma', default=7.0, type=float, help='Source search threshold for images. Default: 7.0')
+    parser.add_argument('-m', '--max_sources', default=None, type=int, metavar='NUM_SRCS',
+                        help='Use the brightest NUM_SRCS stars of each image. Default: all (at most 4096).')
+    parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
+    return parser.parse_args(argv)
+
+
+def _is_source_list(path):
+    from astrophotography_amd import fitsio
+    try:
+        fitsio.read_table(path, 'AP_L1MAG')
+    except KeyError:
+        return False
+    return True
+
+
+def main(args=None):
+    p = command_line_opts(args)
+    from astrophotography_amd.core.ApRegister import ApRegister
+    files = [p.reference] + list(p.sources)
+    kinds = [_is_source_list(f) for f in files]
+    if any(kinds) and not all(kinds):
+        raise RuntimeError('Error, give either images or source lists, not both.')
+    reg = ApRegister(p.loglevel, K=p.nbright, eps=p.eps, match_radius=p.match_radius, model=p.model, allow_mirror=p.allow_mirror)
+    if all(kinds):
+        reg.register_source_lists(files)
+    else:
+        reg.register_images(files, search_fwhm=p.search_fwhm, search_nsigma=p.search_nsigma, max_sources=p.max_sources)
+    reg.write_transforms(p.output, skip_failed=p.skip_failed)
+    return 0
+
+
+if __name__ == '__main__':
+    try:
+        status = main()
+    except Exception:
+        logging.getLogger(__name__).critical('Shutting down due to fatal error')
+        raise
+    else:
+        raise SystemExit(status)

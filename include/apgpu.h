@@ -33,7 +33,7 @@ extern "C" {
 #define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form);
                                        additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes);
                                        apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32;
-                                       apgpu_gauss2d_fit_f32 */
+                                       apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match */
 
 /* error codes */
 #define APGPU_OK            0
@@ -573,6 +573,40 @@ int apgpu_aperture_phot_f32(const float *data, int64_t height, int64_t width, co
 int apgpu_gauss2d_fit_f32(const float *img, int64_t height, int64_t width, const int32_t *box_y, const int32_t *box_x,
                           const double *init, int32_t n, int32_t box_width, int32_t max_iter, double *out_rec, int32_t *out_ok,
                           void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F8  ApRegister: relative registration of frames from their star lists by triangle similarity (Groth 1986, Valdes et al.
+ *     1995).  The reference has no such step (it sends the list to astrometry.net); the rule is this project's own and is
+ *     restated in tests/register_model.py (parity unpinned, the truth is a known synthetic transform).
+ *     xy [n_frames][max_stars][2] float64 (x = column, y = row, 0-based, integer = pixel centre), count [n_frames] int32 the
+ *     valid leading entries of each list, brightest first; frame 0 is the reference.  One launch covers all frames.  No
+ *     workspace.
+ *
+ *     apgpu_triangle_build: every i < j < k among the first min(count[f], k) stars of frame f.  Squared sides dx*dx + dy*dy;
+ *       sorted a2 >= b2 >= c2 by a stable sort of (side opposite i, side opposite j, side opposite k); x = sqrt(b2 / a2),
+ *       y = sqrt(c2 / a2); v0, v1, v2 the vertices opposite the shortest, middle and longest side; orientation the sign (-1, 0,
+ *       1) of (v1 - v0) x (v2 - v0).  Kept iff c2 >= min_side^2, y >= 0.1, x <= 0.98 and y <= 0.98 x.  Kept triangles of frame
+ *       f go to tri_xy [f][tri_capacity][2] (x, y) and tri_v [f][tri_capacity] (v0 | v1 << 8 | v2 << 16 | (orientation + 1) <<
+ *       24) in no particular order, their number to tri_count [f].  3 <= k <= APGPU_REGISTER_MAX_K and tri_capacity >=
+ *       k (k-1) (k-2) / 6 (APGPU_EINVAL otherwise).
+ *     apgpu_triangle_vote: for every frame f >= 1 and every (triangle r of frame 0, triangle t of frame f) with |x_r - x_t| <=
+ *       eps and |y_r - y_t| <= eps (inclusive) and, unless allow_mirror, equal orientation: votes [f][v_r][v_t] += 1 for the
+ *       three canonical vertex pairs.  votes [n_frames][k][k] int32 is zeroed by the call; votes [0] stays zero.  Integer
+ *       sums: the result does not depend on how the work is split, and is the same on every run.
+ *     apgpu_nearest_match: transforms [n_frames][6] float64, p = T_f(r) = ((a0 x + a1 y) + a2, (a3 x + a4 y) + a5) for a
+ *       reference star r.  fwd_idx [f][i] = the star j of frame f nearest to T_f(r_i) with d2 = dx*dx + dy*dy <= radius^2
+ *       (inclusive), fwd_d2 [f][i] that d2; bwd_idx [f][j] = the reference star i whose T_f(r_i) is nearest to star j of frame
+ *       f, bwd_d2 [f][j] its d2.  Ties go to the lower index.  No star inside the radius, or an entry at or beyond the list's
+ *       count: -1 and +inf.  All four outputs are [n_frames][max_stars]; max_stars <= APGPU_REGISTER_MAX_STARS.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_REGISTER_MAX_K 64
+#define APGPU_REGISTER_MAX_STARS 4096
+int apgpu_triangle_build(const double *xy, const int32_t *count, int32_t n_frames, int32_t max_stars, int32_t k, double min_side,
+                         int32_t tri_capacity, double *tri_xy, int32_t *tri_v, int32_t *tri_count, void *stream);
+int apgpu_triangle_vote(const double *tri_xy, const int32_t *tri_v, const int32_t *tri_count, int32_t n_frames,
+                        int32_t tri_capacity, int32_t k, double eps, int32_t allow_mirror, int32_t *votes, void *stream);
+int apgpu_nearest_match(const double *xy, const int32_t *count, const double *transforms, int32_t n_frames, int32_t max_stars,
+                        double radius, int32_t *fwd_idx, double *fwd_d2, int32_t *bwd_idx, double *bwd_d2, void *stream);
 
 #ifdef __cplusplus
 }
