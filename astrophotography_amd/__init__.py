@@ -24,6 +24,7 @@ _LAZY = {
     'ApFindStars': ('.core.ApFindStars', 'ApFindStars'),
     'ApMeasureStars': ('.core.ApMeasureStars', 'ApMeasureStars'),
     'ApRegister': ('.core.ApRegister', 'ApRegister'),
+    'ApComposite': ('.core.ApComposite', 'ApComposite'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

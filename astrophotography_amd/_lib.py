@@ -21,6 +21,7 @@ STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_O
 E_INVAL, E_UNSUPPORTED, E_LAUNCH, E_WORKSPACE = -1, -2, -3, -4
 GAUSS2D_REC, GAUSS2D_MAX_BOX = 20, 76                   # APGPU_GAUSS2D_REC, APGPU_GAUSS2D_MAX_BOX
 REGISTER_MAX_K, REGISTER_MAX_STARS = 64, 4096           # APGPU_REGISTER_MAX_K, APGPU_REGISTER_MAX_STARS
+COMPOSITE_MAX_VARIANTS, TONE_TABLE_LEN = 16, 10241      # APGPU_COMPOSITE_MAX_VARIANTS, APGPU_TONE_TABLE_LEN
 
 
 class ApGpuError(RuntimeError):
@@ -131,6 +132,11 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     'apgpu_nearest_match': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_quantile_levels_ws_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'apgpu_quantile_levels_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    'apgpu_composite_rgb': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1668,3 +1668,90 @@ def register_lists(xy, count, K=40, eps=0.002, min_side=5.0, match_radius=3.0, m
         if len(pairs[f]) >= max(3, len(seeds[f])):
             out['coeffs'][f], out['ok'][f], out['rms'][f] = A[f], True, rms[f]
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F9: ApComposite - colour composites of three co-added planes (csrc/composite.hip; STIFF absent, parity unpinned)
+TONE_OCTAVES, TONE_KNOTS = 40, 256
+
+
+def _planes3(planes):
+    _need_cuda(planes)
+    if planes.dim() != 3 or planes.shape[0] != 3 or planes.shape[1] < 1 or planes.shape[2] < 1:
+        raise ValueError('planes must be [3, H, W] (red, green, blue), got %s' % (tuple(planes.shape),))
+    return _f32c(planes, 'planes')
+
+
+def quantile_levels(planes, q, manual=None):
+    """Exact order statistics of the finite values of each channel: planes [3, H, W] float32, q [3, 2] (min and max quantile per
+    channel, 0 .. 1), manual [3, 2] or None (an entry that is not NaN replaces that level).  The level of q is
+    v[floor(q (n - 1))] of the sorted finite values (np.quantile, method='lower'); no finite value: NaN.
+
+    Returns (levels float32 [3, 2], n_finite int64 [3]), both on the device: nothing is read back."""
+    planes = _planes3(planes)
+    qa = np.array(np.broadcast_to(np.asarray(q, np.float64), (3, 2)))
+    if not np.all((qa >= 0.0) & (qa <= 1.0)):
+        raise ValueError('quantiles must lie in 0 .. 1, got %s' % (qa.tolist(),))
+    dev = planes.device
+    qd = torch.from_numpy(qa).to(dev)
+    md = None
+    if manual is not None:
+        md = torch.from_numpy(np.array(np.broadcast_to(np.asarray(manual, np.float32), (3, 2)))).to(dev)
+    H, W = int(planes.shape[1]), int(planes.shape[2])
+    lib = _lib.load()
+    ws_bytes = lib.apgpu_quantile_levels_ws_bytes(H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    levels = torch.empty((3, 2), dtype=torch.float32, device=dev)
+    n_finite = torch.empty(3, dtype=torch.int64, device=dev)
+    check(lib.apgpu_quantile_levels_f32(_ptr(planes), H, W, _ptr(qd), _ptr(md), _ptr(levels), _ptr(n_finite), _ptr(ws), ws_bytes,
+                                        _stream()))
+    return levels, n_finite
+
+
+def tone_table(gamma=2.2, gamma_fac=1.0, gamma_type='POWER-LAW'):
+    """The float32 table of G(Y) = T(Y) / Y for the luminance curve T(Y) = Y^(1 / (gamma gamma_fac)) (STIFF's POWER-LAW gamma
+    type; any other raises ValueError): 256 knots per octave over 2^-40 .. 2^0 and one closing knot for Y = 1, each the float64
+    value at the knot rounded once to float32.  Host array [10241]; composite_rgb looks it up by the bits of Y."""
+    if str(gamma_type).upper() != 'POWER-LAW':
+        raise ValueError('gamma type %r is not supported: POWER-LAW only' % (gamma_type,))
+    g = float(gamma) * float(gamma_fac)
+    if not (g > 0.0 and np.isfinite(g)):
+        raise ValueError('gamma * gamma_fac must be positive and finite, got %r' % (g,))
+    e = np.arange(-TONE_OCTAVES, 0, dtype=np.float64)[:, None]
+    m = np.arange(TONE_KNOTS, dtype=np.float64)[None, :]
+    y = np.concatenate([(np.exp2(e) * (1.0 + m / TONE_KNOTS)).ravel(), [1.0]])
+    table = (np.power(y, 1.0 / g) / y).astype(np.float32)
+    assert table.size == _lib.TONE_TABLE_LEN
+    return table
+
+
+def composite_rgb(planes, levels, tables, colour_sat, bits=8, flip=True, out=None):
+    """V colour composites from one read of planes [3, H, W] float32: levels [3, 2] float32 (device: quantile_levels), tables
+    [V, 10241] float32 (tone_table per variant; host or device), colour_sat [V].  Returns out [V, H, W, 3] uint8 (bits = 8) or
+    uint16 (bits = 16), interleaved RGB; flip (STIFF's orientation): output row r is FITS row H - 1 - r.  V <= 16.  The
+    per-pixel arithmetic is DESIGN 4.3f / include/apgpu.h."""
+    planes = _planes3(planes)
+    dev = planes.device
+    if bits not in (8, 16):
+        raise ValueError('bits must be 8 or 16, got %r' % (bits,))
+    tables = torch.as_tensor(tables, dtype=torch.float32).to(dev).contiguous()
+    if tables.dim() == 1:
+        tables = tables[None]
+    sat = np.ascontiguousarray(np.asarray(colour_sat, np.float32).reshape(-1))
+    V = int(tables.shape[0])
+    if tables.dim() != 2 or tables.shape[1] != _lib.TONE_TABLE_LEN:
+        raise ValueError('tables must be [V, %d], got %s' % (_lib.TONE_TABLE_LEN, tuple(tables.shape)))
+    if not 1 <= V <= _lib.COMPOSITE_MAX_VARIANTS or sat.size != V:
+        raise ValueError('%d tables and %d saturations: 1 .. %d variants, one saturation each' % (V, sat.size, _lib.COMPOSITE_MAX_VARIANTS))
+    levels = torch.as_tensor(levels, dtype=torch.float32).to(dev).contiguous()
+    if tuple(levels.shape) != (3, 2):
+        raise ValueError('levels must be [3, 2], got %s' % (tuple(levels.shape),))
+    H, W = int(planes.shape[1]), int(planes.shape[2])
+    dt = torch.uint8 if bits == 8 else torch.uint16
+    if out is None:
+        out = torch.empty((V, H, W, 3), dtype=dt, device=dev)
+    elif out.dtype != dt or tuple(out.shape) != (V, H, W, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError('out must be a contiguous device tensor [%d, %d, %d, 3] of %s' % (V, H, W, dt))
+    check(_lib.load().apgpu_composite_rgb(_ptr(planes), H, W, _ptr(levels), _ptr(tables), sat.ctypes.data_as(C.POINTER(C.c_float)), V,
+                                          int(bits), int(bool(flip)), _ptr(out), _stream()))
+    return out

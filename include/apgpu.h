@@ -33,7 +33,8 @@ extern "C" {
 #define APGPU_VERSION 130           /* 0.1.3: apgpu_resample_stack_sigclip, APGPU_STACK_NONFINITE_UNCLIPPED, apgpu_combine_ccdproc_f64(form);
                                        additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes);
                                        apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32;
-                                       apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match */
+                                       apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match;
+                                       apgpu_quantile_levels_f32(_ws_bytes), apgpu_composite_rgb */
 
 /* error codes */
 #define APGPU_OK            0
@@ -607,6 +608,39 @@ int apgpu_triangle_vote(const double *tri_xy, const int32_t *tri_v, const int32_
                         int32_t tri_capacity, int32_t k, double eps, int32_t allow_mirror, int32_t *votes, void *stream);
 int apgpu_nearest_match(const double *xy, const int32_t *count, const double *transforms, int32_t n_frames, int32_t max_stars,
                         double radius, int32_t *fwd_idx, double *fwd_d2, int32_t *bwd_idx, double *bwd_d2, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F9  ApComposite: the colour composite of three co-added planes, the step scripts/composite_all.sh hands to the external
+ *     program STIFF.  STIFF is not in the reference tree, so the arithmetic below is this project's own definition, restated in
+ *     tests/composite_model.py (parity unpinned).  planes [3][height][width] float32 (red, green, blue), all
+ *     float32 arithmetic in the stated order, no contraction.
+ *
+ *     apgpu_quantile_levels_f32: q [3][2] float64 (min and max quantile of each channel, 0 .. 1), manual [3][2] float32 or NULL
+ *       (an entry that is not NaN replaces that level).  With v[0 .. n) the finite values of a channel in ascending order of
+ *       their order-preserving keys (-0.0 below +0.0), the level of q is v[floor(q (n - 1))], the product in float64
+ *       (np.quantile, method 'lower'): an exact order statistic by radix select, all six in the same four reads of the planes,
+ *       no host synchronisation.  n = 0: NaN.  levels [3][2] float32 (lo, hi per channel) and n_finite [3] int64 are written on
+ *       the device.  The workspace is small and does not depend on the image size.
+ *     apgpu_composite_rgb: n_variants (1 .. APGPU_COMPOSITE_MAX_VARIANTS) images from one read of the planes.  Variant v has a
+ *       tone table tables [v][APGPU_TONE_TABLE_LEN] float32 and a saturation colour_sat_host [v] (HOST array).  Per pixel, with
+ *       pos(a) = a > 0 ? a : 0 (NaN gives 0):
+ *           scale_c = hi_c > lo_c ? 1 / (hi_c - lo_c) : 0         (IEEE division; NaN levels give 0)
+ *           s_c = pos((x_c - lo_c) scale_c);   Y = ((s_0 + s_1) + s_2) float32(1/3)
+ *           c_c = pos(Y + sat (s_c - Y));      o_c = c_c G(Y) < 1 ? c_c G(Y) : 1
+ *           pixel_c = (unsigned)(o_c (2^bits - 1) + 0.5f);        any x_c not finite: the pixel is black in every variant
+ *       G(Y) = T(Y) / Y of the luminance curve T comes from the table, indexed by the bits b of min(Y, 1): cell i = (b >> 15) -
+ *       ((127 - 40) << 8) (256 knots per octave from 2^-40, entry 10240 = Y = 1), t = float32(b & 0x7fff) 2^-15, G = G[i] + t
+ *       (G[i + 1] - G[i]) (subtract, multiply, add; at the closing knot t = 0 and G[i + 1] is not read); Y < 2^-40: G = 0.
+ *       out [n_variants][height][width][3] uint8 (bits 8) or uint16 (bits 16), interleaved RGB; flip != 0: output row r is
+ *       plane row height - 1 - r (FITS rows run bottom to top).  planes and out 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_COMPOSITE_MAX_VARIANTS 16
+#define APGPU_TONE_TABLE_LEN 10241
+size_t apgpu_quantile_levels_ws_bytes(int64_t height, int64_t width);
+int apgpu_quantile_levels_f32(const float *planes, int64_t height, int64_t width, const double *q, const float *manual,
+                              float *levels, int64_t *n_finite, void *ws, size_t ws_bytes, void *stream);
+int apgpu_composite_rgb(const float *planes, int64_t height, int64_t width, const float *levels, const float *tables,
+                        const float *colour_sat_host, int32_t n_variants, int32_t bits, int32_t flip, void *out, void *stream);
 
 #ifdef __cplusplus
 }
