@@ -25,6 +25,7 @@ _LAZY = {
     'ApMeasureStars': ('.core.ApMeasureStars', 'ApMeasureStars'),
     'ApRegister': ('.core.ApRegister', 'ApRegister'),
     'ApComposite': ('.core.ApComposite', 'ApComposite'),
+    'ApDebayer': ('.core.ApDebayer', 'ApDebayer'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -137,6 +137,10 @@ SIGNATURES = {
                                             C.c_void_p, C.c_size_t, C.c_void_p]),
     'apgpu_composite_rgb': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int32,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_bayer_demosaic': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_bayer_channel_sums': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                           C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

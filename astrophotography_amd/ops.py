@@ -1755,3 +1755,133 @@ def composite_rgb(planes, levels, tables, colour_sat, bits=8, flip=True, out=Non
     check(_lib.load().apgpu_composite_rgb(_ptr(planes), H, W, _ptr(levels), _ptr(tables), sat.ctypes.data_as(C.POINTER(C.c_float)), V,
                                           int(bits), int(bool(flip)), _ptr(out), _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F10: ApDebayer - Bayer demosaic, white-balance scaling and the sums behind the white balance (csrc/demosaic.hip, DESIGN 4.3g;
+# LibRaw absent: the interpolation is this project's definition)
+DEMOSAIC_METHODS = {'bilinear': 0, 'mhc': 1, 'superpixel': 2}
+DEMOSAIC_OUTPUTS = {'rgb': 0, 'rgb_u16': 1, 'grey': 2, 'direct': 3}
+
+
+def bayer_pattern(pattern):
+    """Four ints: the colour (R 0, G1 1, B 2, G2 3) of cell position (r & 1) 2 + (c & 1); ValueError unless it is a Bayer
+    arrangement (a permutation of 0 .. 3 with red and blue on one diagonal)."""
+    try:
+        pat = [int(x) for x in pattern]
+    except (TypeError, ValueError):
+        pat = []
+    if sorted(pat) != [0, 1, 2, 3] or pat.index(0) ^ pat.index(2) != 3:
+        raise ValueError('pattern %r is not a Bayer arrangement: a permutation of 0 .. 3 (R, G1, B, G2) with red and blue on one '
+                         'diagonal' % (pattern,))
+    return pat
+
+
+def _four_f32(x, name):
+    if x is None:
+        return None
+    a = np.asarray(x, np.float64).reshape(-1)
+    if a.size != 4:
+        raise ValueError('%s takes four values (R, G1, B, G2), got %r' % (name, x))
+    return np.ascontiguousarray(a.astype(np.float32))
+
+
+def _f32p(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _bayer_black(black, dtype):
+    blk = _four_f32(black, 'black')
+    if blk is not None and dtype == APGPU_U16 and not np.all((blk == np.floor(blk)) & (blk >= 0) & (blk <= 65535)):
+        raise ValueError('the black levels of uint16 data must be integers 0 .. 65535, got %r' % (black,))
+    return blk
+
+
+def bayer_demosaic(mosaic, pattern=(0, 1, 3, 2), black=None, gain=None, method='mhc', output='rgb', out=None):
+    """Colour planes of Bayer mosaics: mosaic [H, W] or [N, H, W], uint16 or float32; pattern as in bayer_split (a Bayer
+    arrangement); black, gain: four values by colour (R, G1, B, G2) or None.  Every sample is float32(max(raw - black, 0)) gain.
+
+    method  'bilinear', 'mhc' (Malvar-He-Cutler 2004) or 'superpixel' (one pixel per 2 x 2 cell: H and W even, h = H / 2)
+    output  'rgb' float32 [3, h, w]; 'rgb_u16' the same clipped to 0 .. 65535 and truncated; 'grey' float32 [h, w], the CCIR 601
+            luminance of the colours; 'direct' float32 [H, W], the scaled samples themselves (method is ignored)
+
+    A slab gives [N, 3, h, w] or [N, h, w].  out: a contiguous device tensor of that shape and dtype.  The arithmetic is DESIGN
+    4.3g / include/apgpu.h, restated in tests/demosaic_model.py."""
+    _need_cuda(mosaic, out)
+    dt = _raw_dtype(mosaic)
+    if mosaic.dim() not in (2, 3):
+        raise TypeError('mosaic must be [H, W] or [N, H, W], got %s' % (tuple(mosaic.shape),))
+    pat = bayer_pattern(pattern)
+    if method not in DEMOSAIC_METHODS:
+        raise ValueError('method %r is not one of %s' % (method, sorted(DEMOSAIC_METHODS)))
+    if output not in DEMOSAIC_OUTPUTS:
+        raise ValueError('output %r is not one of %s' % (output, sorted(DEMOSAIC_OUTPUTS)))
+    blk, gn = _bayer_black(black, dt), _four_f32(gain, 'gain')
+    mosaic = mosaic.contiguous()
+    single = mosaic.dim() == 2
+    N = 1 if single else int(mosaic.shape[0])
+    H, W = int(mosaic.shape[-2]), int(mosaic.shape[-1])
+    if N < 1 or H < 2 or W < 2:
+        raise ValueError('a mosaic needs at least 2 x 2 pixels and one frame, got %s' % (tuple(mosaic.shape),))
+    h, w = H, W
+    if method == 'superpixel' and output != 'direct':
+        if H % 2 or W % 2:
+            raise ValueError('superpixel needs an even number of rows and columns, got %d x %d' % (H, W))
+        h, w = H // 2, W // 2
+    shape = (3, h, w) if output in ('rgb', 'rgb_u16') else (h, w)
+    shape = shape if single else (N,) + shape
+    odt = torch.uint16 if output == 'rgb_u16' else torch.float32
+    if out is None:
+        out = torch.empty(shape, dtype=odt, device=mosaic.device)
+    elif out.dtype != odt or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError('out must be a contiguous device tensor %s of %s' % (shape, odt))
+    check(_lib.load().apgpu_bayer_demosaic(_ptr(mosaic), dt, N, H, W, (C.c_int32 * 4)(*pat), _f32p(blk), _f32p(gn),
+                                           DEMOSAIC_METHODS[method], DEMOSAIC_OUTPUTS[output], _ptr(out), _stream()))
+    return out
+
+
+def bayer_channel_sums(mosaic, pattern, black=None, region=None):
+    """The device half of RawConv._get_whitebalance_from_region (RawConv.py:291-366): for each colour (R, G1, B, G2) the sum of
+    max(raw - black, 0) over its sites in region = (rowmin, rowmax, colmin, colmax), inclusive and clamped to the image (None: the
+    whole image), and their number.  mosaic [H, W] uint16 gives exact uint64 sums; float32 gives float64 sums and counts of the
+    finite samples.  Returns (sums [4], counts [4] int64) on the device."""
+    _need_cuda(mosaic)
+    dt = _raw_dtype(mosaic)
+    if mosaic.dim() != 2 or mosaic.shape[0] < 2 or mosaic.shape[1] < 2:
+        raise TypeError('mosaic must be [H, W] of at least 2 x 2, got %s' % (tuple(mosaic.shape),))
+    pat = bayer_pattern(pattern)
+    blk = _bayer_black(black, dt)
+    mosaic = mosaic.contiguous()
+    H, W = int(mosaic.shape[0]), int(mosaic.shape[1])
+    rect = [0, H, 0, W] if region is None else [int(v) for v in region]
+    if len(rect) != 4:
+        raise ValueError('region takes rowmin, rowmax, colmin, colmax, got %r' % (region,))
+    sums = torch.empty(4, dtype=torch.uint64 if dt == APGPU_U16 else torch.float64, device=mosaic.device)
+    counts = torch.empty(4, dtype=torch.int64, device=mosaic.device)
+    check(_lib.load().apgpu_bayer_channel_sums(_ptr(mosaic), dt, H, W, (C.c_int32 * 4)(*pat), _f32p(blk), (C.c_int64 * 4)(*rect),
+                                               _ptr(sums), _ptr(counts), _stream()))
+    return sums, counts
+
+
+def whitebalance_from_sums(sums, counts):
+    """Four float64 gains from the four sums and counts: avg = sum / count, gain = max(avg) / avg (RawConv.py:315-331).  A colour
+    with no pixels or avg <= 0 raises ValueError (the reference divides by zero there)."""
+    avg = []
+    for name, s, n in zip(('R', 'G1', 'B', 'G2'), sums, counts):
+        if int(n) < 1:
+            raise ValueError('white balance: colour %s has no valid pixels in the region' % name)
+        a = float(s) / float(int(n))
+        if not a > 0.0:
+            raise ValueError('white balance: colour %s has a mean of %r in the region' % (name, a))
+        avg.append(a)
+    top = max(avg)
+    return np.array([top / a for a in avg], np.float64)
+
+
+def bayer_whitebalance(mosaic, pattern, black=None, region=None):
+    """RawConv.get_whitebalance('auto' | 'region[...]'): four float64 gains (R, G1, B, G2) from bayer_channel_sums; the eight
+    numbers are read back and divided on the host."""
+    sums, counts = bayer_channel_sums(mosaic, pattern, black, region)
+    s = sums.cpu()
+    s = [int(v) for v in s.view(torch.int64).tolist()] if s.dtype == torch.uint64 else s.tolist()
+    return whitebalance_from_sums(s, counts.cpu().tolist())

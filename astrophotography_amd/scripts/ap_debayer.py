@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""ap_debayer - red, green and blue FITS images (or a luminance) from the FITS Bayer mosaic of a one-shot-colour camera, on the
+GPU: the arithmetic of the reference's `dksraw rgb` and `dksraw grey` (cli.py:175-275, core/RawConv.py) for frames that are
+already FITS.
+
+    ap_debayer light_0001.fits light_0001                      ->  light_0001_r.fits  light_0001_g.fits  light_0001_b.fits
+    ap_debayer light_0001.fits x --grey light_0001_lum.fits -w "region[450, 463, 2850, 2863]"
+
+The three images are what ap_find_stars, ap_register, ap_coadd and ap_composite take.  Decoding camera RAW files, EXIF data and
+--renormalize are out of scope."""
+import argparse
+import logging
+
+ALLOWED_WB = ['daylight', 'camera', 'auto', 'region[regspec]', 'user[userspec]']          # cli.py:170
+ALLOWED_METHODS = ['bilinear', 'mhc', 'superpixel']
+PATTERNS = ['RGGB', 'BGGR', 'GRBG', 'GBRG']
+
+
+def command_line_opts(argv):
+    parser = argparse.ArgumentParser(prog='ap_debayer', description='Creates red, green and blue FITS images (or a monochrome '
+                                     'luminance image) from a FITS Bayer mosaic using the specified method and white-balance.')
+    parser.add_argument('infile', metavar='MOSAIC.FITS', help='Input FITS file: one 2-D Bayer mosaic (BITPIX 16 or -32).')
+    parser.add_argument('out_root', metavar='OUT_ROOT', help='Output files are OUT_ROOT_r.fits, OUT_ROOT_g.fits, OUT_ROOT_b.fits (float32).')
+    parser.add_argument('-m', '--method', default='mhc', choices=ALLOWED_METHODS,
+                        help='Method used to interpolate the Bayer sub channels. bilinear: means of the nearest like-coloured '
+                             'neighbours. mhc: Malvar-He-Cutler gradient-corrected linear interpolation (5 x 5). superpixel: one '
+                             'output pixel per 2 x 2 cell, half the size, no interpolation. Default: mhc')
+    parser.add_argument('-w', '--whitebalance', default='auto',
+                        help='Whitebalance to use when convert R, G and B channels. Allowed whitebalance methods are: %s '
+                             'To calculate the whitebalance from the entire image use "auto". To calculate the whitebalance from '
+                             'part of an image use "region" with a region specifier of the form [minrow, maxrow, mincol, maxcol], '
+                             'where the pixel indices are zero-based and inclusive. For example: "region[450, 463, 2850, 2863]". To '
+                             'specify a user selected whitebalance use "user" with a user specifier of form [Rmult, G1mult, Bmult, '
+                             'G2mult]. For example "user[1.85, 1.0, 2.01, 1.0]". The region and user options should be enclosed in '
+                             'quotes to prevent shell expansion. camera and daylight need LibRaw metadata a FITS file does not carry '
+                             'and are refused. Default: auto' % ALLOWED_WB)
+    parser.add_argument('--keepblack', default=False, action='store_true',
+                        help='Retain the camera band-specific black levels in the data. These are roughly equivalent to a CCD bias '
+                             'level. Default: False')
+    parser.add_argument('--pattern', default=None, choices=PATTERNS, type=str.upper,
+                        help='The colours of the first two pixels of the first two array rows, the rows taken in file order (the '
+                             'first row stored in the file is row 0). Default: the BAYERPAT keyword, shifted by XBAYROFF / YBAYROFF '
+                             'when present; neither given is an error.')
+    parser.add_argument('--black', default=None, nargs=4, type=float, metavar=('R', 'G1', 'B', 'G2'),
+                        help='Black levels subtracted from the four colours. Default: 0 0 0 0')
+    parser.add_argument('--grey', default=None, metavar='OUT.FITS',
+                        help='Write the monochrome luminance image to OUT.FITS instead of the three colour images.')
+    parser.add_argument('--luminance', default='linear', choices=['linear', 'direct'],
+                        help='With --grey. linear: the CCIR 601 luma coefficients applied to the interpolated colours. direct: does '
+                             'not perform any de-Bayer calculation, each pixel is set to its whitebalance-scaled value from which ever '
+                             'RGBG subband it came from. Default: linear')
+    parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
+    return parser.parse_args(argv)
+
+
+def main(args=None):
+    p = command_line_opts(args)
+    from astrophotography_amd.core.ApDebayer import ApDebayer
+    ApDebayer(p.loglevel).debayer_files(p.infile, p.out_root, method=p.method, wb_method=p.whitebalance, subtract_black=not p.keepblack,
+                                        black=p.black, pattern=p.pattern, grey=p.grey, luminance_method=p.luminance)
+    return 0
+
+
+if __name__ == '__main__':
+    try:
+        status = main()
+    except Exception:
+        logging.getLogger(__name__).critical('Shutting down due to fatal error')
+        raise
+    else:
+        raise SystemExit(status)

@@ -34,7 +34,8 @@ extern "C" {
                                        additive since: apgpu_axis_nanmedian, apgpu_sliding_clipped_stats(_ws_bytes);
                                        apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32;
                                        apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match;
-                                       apgpu_quantile_levels_f32(_ws_bytes), apgpu_composite_rgb */
+                                       apgpu_quantile_levels_f32(_ws_bytes), apgpu_composite_rgb;
+                                       apgpu_bayer_demosaic, apgpu_bayer_channel_sums */
 
 /* error codes */
 #define APGPU_OK            0
@@ -641,6 +642,49 @@ int apgpu_quantile_levels_f32(const float *planes, int64_t height, int64_t width
                               float *levels, int64_t *n_finite, void *ws, size_t ws_bytes, void *stream);
 int apgpu_composite_rgb(const float *planes, int64_t height, int64_t width, const float *levels, const float *tables,
                         const float *colour_sat_host, int32_t n_variants, int32_t bits, int32_t flip, void *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F10 ApDebayer: Bayer demosaic, white-balance scaling and the sums behind the white balance (core/RawConv.py:291-366 white
+ *     balance from the image, :401-486 rgb, :488-587 grey).  The reference leaves the interpolation to LibRaw, which is not in
+ *     its tree, so the arithmetic below is this project's own definition, restated in tests/demosaic_model.py.
+ *     All float32, one rounding per operation in the stated order, no contraction; NaN and inf propagate by IEEE rules.
+ *
+ *     pattern_host [4]: the colour (R 0, G1 1, B 2, G2 3) of cell position (r & 1) 2 + (c & 1), as in A9, here a Bayer arrangement
+ *       (a permutation of 0 .. 3 with red and blue on one diagonal; APGPU_EINVAL otherwise).  black_host, gain_host: [4] float32
+ *       HOST arrays by colour, NULL = zeros / ones; the black levels of uint16 data must be integers 0 .. 65535.
+ *     sample   s(r, c) = float32(max(raw - black[k], 0)) gain[k] with k the colour of the site.  uint16: integer subtraction
+ *       (RawConv._safe_subtract); float32: d = raw - black[k], d < 0 gives 0, NaN stays NaN.
+ *     borders  an index is reflected about the edge sample (-1 -> 1, -2 -> 2, H -> H - 2), folded with period 2 (H - 1), so every
+ *       tap keeps its colour.  height, width >= 2, odd sizes included.
+ *     taps     C the site; N S W E its edge neighbours; NW NE SW SE the diagonals; N2 S2 W2 E2 at distance 2 on the axes;
+ *       ns = N + S, we = W + E, d4 = (NW + NE) + (SW + SE), ns2 = N2 + S2, we2 = W2 + E2, e4 = ns + we, a4 = ns2 + we2.
+ *     BILINEAR    own colour C.  At R/B: G = e4 0.25f, the other of R/B = d4 0.25f.  At G: the colour that shares the row =
+ *       we 0.5f, the colour that shares the column = ns 0.5f.
+ *     MHC         Malvar-He-Cutler 2004 in sixteenths.  Own colour C.  At R/B: G = ((8 C + 4 e4) - 2 a4) 2^-4, the other of R/B =
+ *       ((12 C + 4 d4) - 3 a4) 2^-4.  At G: the colour of the row = (((10 C + 8 we) + ns2) - 2 (d4 + we2)) 2^-4, the colour of
+ *       the column = (((10 C + 8 ns) + we2) - 2 (d4 + ns2)) 2^-4.
+ *     SUPERPIXEL  height and width even; one output pixel per cell: R = s_R, G = (s_G1 + s_G2) 0.5f, B = s_B.
+ *     output      RGB_F32: out [n_frames][3][h][w] float32.  RGB_U16: the same as (uint16)(v > 0 ? (v < 65535 ? v : 65535) : 0),
+ *       truncating, NaN gives 0 (np.clip + astype, RawConv.py:484-486).  GREY_F32: out [n_frames][h][w] = (0.299f R + 0.587f G) +
+ *       0.114f B (CCIR 601, :550).  DIRECT_F32: out [n_frames][height][width] = s, the 'direct' luminance (:533-547); method is
+ *       ignored.  (h, w) = (height, width), halved for SUPERPIXEL.  mosaic and out aligned to their element size; no workspace.
+ *
+ *     The channel sums are the device half of RawConv._get_whitebalance_from_region: rect_host [4] int64 = rowmin, rowmax, colmin,
+ *     colmax, inclusive, clamped to the image.  For each colour, the sum of max(raw - black[k], 0) over its sites inside the
+ *     rectangle and their number: uint16 data gives exact uint64 sums [4]; float32 data gives float64 sums [4] of the finite
+ *     samples (in no fixed order) and counts them.  sums (8 bytes each) and counts [4] int64 are written on the device.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_DEMOSAIC_BILINEAR   0
+#define APGPU_DEMOSAIC_MHC        1
+#define APGPU_DEMOSAIC_SUPERPIXEL 2
+#define APGPU_DEMOSAIC_RGB_F32    0
+#define APGPU_DEMOSAIC_RGB_U16    1
+#define APGPU_DEMOSAIC_GREY_F32   2
+#define APGPU_DEMOSAIC_DIRECT_F32 3
+int apgpu_bayer_demosaic(const void *mosaic, int32_t dtype, int64_t n_frames, int64_t height, int64_t width, const int32_t *pattern_host,
+                         const float *black_host, const float *gain_host, int32_t method, int32_t output, void *out, void *stream);
+int apgpu_bayer_channel_sums(const void *mosaic, int32_t dtype, int64_t height, int64_t width, const int32_t *pattern_host,
+                             const float *black_host, const int64_t *rect_host, void *sums, int64_t *counts, void *stream);
 
 #ifdef __cplusplus
 }
