@@ -26,6 +26,7 @@ _LAZY = {
     'ApRegister': ('.core.ApRegister', 'ApRegister'),
     'ApComposite': ('.core.ApComposite', 'ApComposite'),
     'ApDebayer': ('.core.ApDebayer', 'ApDebayer'),
+    'ApContinuumSubtract': ('.core.ApContinuumSubtract', 'ApContinuumSubtract'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -1885,3 +1885,251 @@ def bayer_whitebalance(mosaic, pattern, black=None, region=None):
     s = sums.cpu()
     s = [int(v) for v in s.view(torch.int64).tolist()] if s.dtype == torch.uint64 else s.tolist()
     return whitebalance_from_sums(s, counts.cpu().tolist())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F11: ApContinuumSubtract - PSF matching, the scale and offset of the continuum, the subtraction (csrc/continuum.hip, DESIGN
+# 4.3h; the reference lists the stage as not yet built: the arithmetic is this project's definition)
+BLUR_MAX_RADIUS, BLUR_TILE_H, BLUR_TILE_W = _lib.BLUR_MAX_RADIUS, _lib.BLUR_TILE_H, _lib.BLUR_TILE_W
+FWHM_TO_SIGMA = 0.42466090014400953                    # 1 / (2 sqrt(2 ln 2))
+
+
+def gauss_taps(sigma, radius=None):
+    """float64 taps w[0 .. 2R] of a Gaussian of `sigma` pixels, exp(-(k - R)^2 / (2 sigma^2)) normalised to sum 1, R = ceil(4 sigma)
+    (at least 1) unless given.  sigma = 0 or radius = 0: the identity {1}.  R > 32 raises ValueError."""
+    import math
+    sigma = float(sigma)
+    if not sigma >= 0.0 or not math.isfinite(sigma):
+        raise ValueError('sigma must be finite and >= 0, got %r' % sigma)
+    if radius is None:
+        radius = 0 if sigma == 0.0 else max(1, int(math.ceil(4.0 * sigma)))
+    radius = int(radius)
+    if radius < 0 or radius > BLUR_MAX_RADIUS:
+        raise ValueError('a blur of sigma = %g pixels needs a radius of %d, the kernel holds %d' % (sigma, radius, BLUR_MAX_RADIUS))
+    if radius == 0 or sigma == 0.0:
+        w = np.zeros(2 * radius + 1)
+        w[radius] = 1.0
+        return w
+    k = np.arange(2 * radius + 1, dtype=np.float64) - radius
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return w / w.sum()
+
+
+def gauss_blur(data, sigma, min_weight=0.5, out=None):
+    """The normalised, separable Gaussian blur of a float32 image [H, W] whose NaN / inf pixels mean "no data": every output is
+    the weighted mean of the valid pixels under the kernel, NaN where the pixel itself is missing or the valid weight is below
+    min_weight.  sigma: pixels, or the float64 taps themselves (an odd number, at most 65).  float64 accumulation in a fixed
+    order (include/apgpu.h F11; tests/continuum_model.py)."""
+    data = _image_f32(data)
+    _need_cuda(out)
+    taps = gauss_taps(sigma) if np.ndim(sigma) == 0 else np.ascontiguousarray(np.asarray(sigma, np.float64).reshape(-1))
+    if taps.size % 2 != 1:
+        raise ValueError('the taps must be an odd number of weights, got %d' % taps.size)
+    R = (taps.size - 1) // 2
+    if R > BLUR_MAX_RADIUS:
+        raise ValueError('a blur radius of %d, the kernel holds %d' % (R, BLUR_MAX_RADIUS))
+    if not float(min_weight) >= 0.0:
+        raise ValueError('min_weight must be >= 0, got %r' % (min_weight,))
+    if out is None:
+        out = torch.empty_like(data)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(data.shape) or not out.is_contiguous() or out.data_ptr() == data.data_ptr():
+        raise ValueError('out must be a contiguous float32 device tensor of the image shape, distinct from the input')
+    check(_lib.load().apgpu_gauss_blur_norm_f32(_ptr(data), data.shape[0], data.shape[1], taps.ctypes.data_as(C.POINTER(C.c_double)), R,
+                                                float(min_weight), _ptr(out), _stream()))
+    return out
+
+
+def _pair(n, c, mask=None):
+    n, c = _image_f32(n, 'n'), _image_f32(c, 'c')
+    if tuple(n.shape) != tuple(c.shape):
+        raise ValueError('the two images must have one shape, got %s and %s' % (tuple(n.shape), tuple(c.shape)))
+    if mask is not None:
+        _need_cuda(mask)
+        if tuple(mask.shape) != tuple(n.shape):
+            raise ValueError('mask must have the image shape')
+        mask = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    return n, c, mask
+
+
+def pair_moments(n, c, s=0.0, b=0.0, lo=-float('inf'), hi=float('inf'), mask=None, ws=None):
+    """float64 device tensor [6] = count, sum c, sum n, sum c c, sum c n, sum n n over the pixel pairs that are finite in both
+    float32 images, unmasked (mask == 0) and whose residual r = n - (s c + b) lies in [lo, hi] (inclusive; float64).  The same
+    input gives the same bits on every run.  ws: a uint8 workspace from an earlier call's size, or None."""
+    n, c, mask = _pair(n, c, mask)
+    lib = _lib.load()
+    need = lib.apgpu_pair_moments_ws_bytes(n.numel())
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=n.device)
+    out = torch.empty(6, dtype=torch.float64, device=n.device)
+    check(lib.apgpu_pair_moments_f64(_ptr(n), _ptr(c), _ptr(mask), n.numel(), float(s), float(b), float(lo), float(hi), _ptr(out), _ptr(ws),
+                                     ws.numel(), _stream()))
+    return out
+
+
+def linear_combine(x, y, ca, cb, c0, out=None):
+    """out = (float32(ca x) + float32(cb y)) + c0 in float32, NaN where x or y is not finite; y None: float32(ca x) + c0.  Tensors
+    of any one shape; out may be x or y."""
+    _need_cuda(x, y, out)
+    x = _f32c(x, 'x')
+    y = _f32c(y, 'y')
+    if x.numel() == 0 or (y is not None and tuple(y.shape) != tuple(x.shape)):
+        raise ValueError('x and y must be non-empty tensors of one shape')
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous float32 device tensor of the shape of x')
+    check(_lib.load().apgpu_linear_combine_f32(_ptr(x), _ptr(y), float(np.float32(ca)), float(np.float32(cb)), float(np.float32(c0)), _ptr(out),
+                                               x.numel(), _stream()))
+    return out
+
+
+def _line_from_moments(mom, fixed_scale=None):
+    """The straight line n = s c + b from the six moments, in centred form (float64 on the host)."""
+    import math
+    cnt, sc, sy, scc, scy, syy = (float(v) for v in mom)
+    if cnt < 3:
+        raise RuntimeError('continuum fit: %d valid pixel pairs survive, at least 3 are needed' % int(cnt))
+    cbar, ybar = sc / cnt, sy / cnt
+    Scc, Scy, Syy = scc - sc * cbar, scy - sc * ybar, syy - sy * ybar
+    if fixed_scale is None:
+        if not Scc > 0.0:
+            raise RuntimeError('continuum fit: the continuum image has zero variance over the valid pixels')
+        s = Scy / Scc
+        rss, dof = Syy - s * Scy, cnt - 2.0
+    else:
+        s = float(fixed_scale)
+        rss, dof = (Syy - 2.0 * s * Scy) + s * s * Scc, cnt - 1.0
+    rss = max(rss, 0.0)
+    var = rss / dof
+    se_s = math.sqrt(var / Scc) if fixed_scale is None else 0.0
+    se_b = math.sqrt(var * (1.0 / cnt + cbar * cbar / Scc)) if fixed_scale is None else math.sqrt(var / cnt)
+    return dict(s=s, b=ybar - s * cbar, sigma=math.sqrt(rss / cnt), n=int(cnt), se_s=se_s, se_b=se_b)
+
+
+def _truncated_gauss(alpha, beta):
+    """(mean, variance) of a unit Gaussian cut to [alpha, beta]."""
+    import math
+    phi = lambda x: math.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi) if math.isfinite(x) else 0.0      # noqa: E731
+    Phi = lambda x: 0.5 * math.erfc(-x / math.sqrt(2.0))                                               # noqa: E731
+    Z = Phi(beta) - Phi(alpha)
+    pa, pb = phi(alpha), phi(beta)
+    mean = (pa - pb) / Z
+    return mean, 1.0 + ((alpha * pa if math.isfinite(alpha) else 0.0) - (beta * pb if math.isfinite(beta) else 0.0)) / Z - mean * mean
+
+
+def truncation_shift(sigma_lower=3.0, sigma_upper=2.0):
+    """The mean of a unit Gaussian cut to [-sigma_lower, sigma_upper]: -0.0508 for the defaults."""
+    return _truncated_gauss(-float(sigma_lower), float(sigma_upper))[0]
+
+
+def gaussian_truncation(lo, hi, mean_kept, sigma_kept):
+    """(mu, sigma0) of the Gaussian whose part inside [lo, hi] has the mean mean_kept and the standard deviation sigma_kept: the
+    truncated Gaussian's closed-form mean and variance, solved for the Gaussian by fixed-point rounds."""
+    import math
+    if not (math.isfinite(lo) or math.isfinite(hi)) or not sigma_kept > 0.0:
+        return mean_kept, sigma_kept
+    mu, s0 = mean_kept, sigma_kept
+    for _ in range(200):
+        m, var = _truncated_gauss((lo - mu) / s0, (hi - mu) / s0)
+        ns0 = sigma_kept / math.sqrt(var)
+        nmu = mean_kept - ns0 * m
+        done = abs(ns0 - s0) <= 1e-13 * s0 and abs(nmu - mu) <= 1e-13 * s0
+        mu, s0 = nmu, ns0
+        if done:
+            break
+    return mu, s0
+
+
+def continuum_scale_pixels(n, c, mask=None, sigma_lower=3.0, sigma_upper=2.0, maxiters=10, fixed_scale=None):
+    """The iteratively clipped straight-line fit n = s c + b over the valid pixel pairs of two float32 device images: the unclipped
+    fit first, then bounds [-sigma_lower sigma, +sigma_upper sigma] on the residuals about the last line (sigma the rms residual of
+    the kept pixels) until the count stands still or maxiters fits were made; one launch and one 48-byte read-back per round.
+    Emission only adds to n, hence the tighter upper bound; b is then corrected for the shift an asymmetric cut gives the mean of
+    Gaussian noise (gaussian_truncation).  fixed_scale: s is held and only b is fitted.
+
+    Returns dict(s, b, b_uncorrected, sigma, sigma0, shift, n, n_unclipped, iterations, se_s, se_b, lo, hi)."""
+    n, c, mask = _pair(n, c, mask)
+    ws = torch.empty(_lib.load().apgpu_pair_moments_ws_bytes(n.numel()), dtype=torch.uint8, device=n.device)
+    lo, hi = -float('inf'), float('inf')
+    fit = _line_from_moments(pair_moments(n, c, 0.0, 0.0, lo, hi, mask, ws).cpu().numpy(), fixed_scale)
+    n_unclipped, prev_b, count, iters = fit['n'], fit['b'], fit['n'], 0
+    for _ in range(int(maxiters)):
+        nlo, nhi = -float(sigma_lower) * fit['sigma'], float(sigma_upper) * fit['sigma']
+        mom = pair_moments(n, c, fit['s'], fit['b'], nlo, nhi, mask, ws).cpu().numpy()
+        if int(mom[0]) == count:
+            break
+        prev_b = fit['b']
+        fit = _line_from_moments(mom, fixed_scale)
+        lo, hi, count = nlo, nhi, fit['n']
+        iters += 1
+    mu, sigma0 = gaussian_truncation(lo, hi, fit['b'] - prev_b, fit['sigma'])
+    out = dict(fit)
+    out.update(b=prev_b + mu, b_uncorrected=fit['b'], sigma0=sigma0, shift=fit['b'] - (prev_b + mu), iterations=iters, lo=lo, hi=hi,
+               n_unclipped=n_unclipped)
+    return out
+
+
+def _clipped_median(x, sigma=3.0, maxiters=5):
+    x = np.asarray(x, np.float64).ravel()
+    x = x[np.isfinite(x)]
+    for _ in range(int(maxiters)):
+        if x.size == 0:
+            break
+        med, sd = np.median(x), np.std(x)
+        y = x[(x >= med - sigma * sd) & (x <= med + sigma * sd)]
+        if y.size == x.size:
+            break
+        x = y
+    if x.size == 0:
+        return float('nan'), float('nan'), 0
+    return float(np.median(x)), float(np.std(x)), int(x.size)
+
+
+def continuum_scale_stars(n, c, xy, fwhm, peak=None, satlevel=None, min_stars=5, mask=None, sigma_lower=3.0, sigma_upper=2.0,
+                          maxiters=10):
+    """s from the stars, b from the pixels.  Stars are continuum sources: aperture_photometry of both (PSF-matched) float32 device
+    images at the positions xy [k, 2] (x = column, y = row), aperture and annulus from `fwhm` (the broader one; aperture_radii), the
+    flux sky-subtracted by the annulus median.  Kept: both fluxes positive and finite, peak < satlevel where both are given.  s =
+    the sigma-clipped median (3 sigma, 5 rounds, float64 on the host) of F_N / F_C; b from continuum_scale_pixels with s held.
+    Fewer than min_stars kept stars raise RuntimeError.
+
+    Returns the dict of continuum_scale_pixels plus n_stars, n_stars_used, ratio_spread, flux_n, flux_c (NumPy) and se_s =
+    spread / sqrt(stars used)."""
+    import math
+    n, c, mask = _pair(n, c, mask)
+    xy = np.asarray(xy.cpu() if torch.is_tensor(xy) else xy, np.float64).reshape(-1, 2)
+    fn = aperture_photometry(n, xy[:, 0], xy[:, 1], fwhm=fwhm)['aperture_sum'].cpu().numpy()
+    fc = aperture_photometry(c, xy[:, 0], xy[:, 1], fwhm=fwhm)['aperture_sum'].cpu().numpy()
+    keep = np.isfinite(fn) & np.isfinite(fc) & (fn > 0) & (fc > 0)
+    if peak is not None and satlevel is not None:
+        keep &= np.asarray(peak, np.float64).reshape(-1) < float(satlevel)
+    if int(keep.sum()) < int(min_stars):
+        raise RuntimeError('continuum scale from stars: %d usable stars, at least %d are needed' % (int(keep.sum()), int(min_stars)))
+    s, spread, used = _clipped_median(fn[keep] / fc[keep])
+    out = continuum_scale_pixels(n, c, mask, sigma_lower, sigma_upper, maxiters, fixed_scale=s)
+    out.update(se_s=spread / math.sqrt(max(used, 1)), n_stars=int(keep.sum()), n_stars_used=used, ratio_spread=spread, flux_n=fn, flux_c=fc,
+               keep=keep)
+    return out
+
+
+def psf_match(n, c, fwhm_n, fwhm_c, threshold=0.05, min_weight=0.5):
+    """Brings two float32 device images to one PSF: the sharper one is blurred with a Gaussian of sigma_k = sqrt(sigma_broad^2 -
+    sigma_sharp^2), sigma = FWHM / (2 sqrt(2 ln 2)); |FWHM_n - FWHM_c| < threshold blurs nothing.  A sigma_k that needs a radius
+    above 32 raises ValueError naming the FWHMs.  Returns (n', c', dict(blurred 'narrow' | 'continuum' | None, sigma_k, taps))."""
+    import math
+    n, c, _ = _pair(n, c)
+    fwhm_n, fwhm_c = float(fwhm_n), float(fwhm_c)
+    if not (fwhm_n > 0 and fwhm_c > 0 and math.isfinite(fwhm_n) and math.isfinite(fwhm_c)):
+        raise ValueError('the FWHMs must be positive and finite, got %r and %r' % (fwhm_n, fwhm_c))
+    if abs(fwhm_n - fwhm_c) < float(threshold):
+        return n, c, dict(blurred=None, sigma_k=0.0, taps=None)
+    sn, sc = fwhm_n * FWHM_TO_SIGMA, fwhm_c * FWHM_TO_SIGMA
+    broad, sharp = max(sn, sc), min(sn, sc)
+    sigma_k = math.sqrt(broad * broad - sharp * sharp)
+    try:
+        taps = gauss_taps(sigma_k)
+    except ValueError as exc:
+        raise ValueError('PSF matching FWHM %g to %g: %s' % (fwhm_n, fwhm_c, exc)) from None
+    if sn < sc:
+        return gauss_blur(n, taps, min_weight), c, dict(blurred='narrow', sigma_k=sigma_k, taps=taps)
+    return n, gauss_blur(c, taps, min_weight), dict(blurred='continuum', sigma_k=sigma_k, taps=taps)

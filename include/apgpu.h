@@ -686,6 +686,47 @@ int apgpu_bayer_demosaic(const void *mosaic, int32_t dtype, int64_t n_frames, in
 int apgpu_bayer_channel_sums(const void *mosaic, int32_t dtype, int64_t height, int64_t width, const int32_t *pattern_host,
                              const float *black_host, const int64_t *rect_host, void *sums, int64_t *counts, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F11 ApContinuumSubtract: narrow-band continuum subtraction L = N' - s C' - b (the reference's stage table lists "Continuum
+ *     Subtract" as not yet built, doc/iTelescope_processing.md:8-29, so the arithmetic is this project's own definition, DESIGN
+ *     4.3h, restated in tests/continuum_model.py).  No contraction: every multiply and add below rounds on its own.
+ *
+ *     apgpu_gauss_blur_norm_f32: the normalised, separable blur that matches the sharper image's PSF to the broader one.
+ *       data, out [height][width] float32, 4-byte aligned, distinct; taps_host [2 radius + 1] float64 on the HOST (normally
+ *       exp(-(k - R)^2 / (2 sigma^2)) normalised to sum 1; any weights are taken as they are); 0 <= radius <=
+ *       APGPU_BLUR_MAX_RADIUS (larger: APGPU_EUNSUPPORTED); min_weight >= 0.  valid(y, x) = inside the image and finite.
+ *       row pass     a(y, x) = sum_k w[k] double(v(y, x + k - R)), m(y, x) = sum_k w[k], both over the valid taps only, k
+ *                    ascending, float64 accumulators that start at +0, the product rounded before the sum.
+ *       column pass  A(y, x) = sum_k w[k] a(y + k - R, x), M(y, x) = sum_k w[k] m(y + k - R, x) over the rows inside the image,
+ *                    in the same way.
+ *       out(y, x) = float32(A / M) (IEEE division, then one rounding to float32) where valid(y, x) and M >= min_weight; NaN
+ *       (0x7fc00000) elsewhere: holes keep their footprint and a pixel whose neighbourhood is mostly missing is not
+ *       extrapolated.  radius 0 with taps {1} is the identity with that rule (+-inf become NaN).  One launch, no workspace: a
+ *       workgroup owns a tile of APGPU_BLUR_TILE_H x APGPU_BLUR_TILE_W pixels and stages it with a halo of `radius` in LDS;
+ *       image edges and tile edges take the same path (out-of-image taps are staged as NaN).
+ *
+ *     apgpu_pair_moments_f64: the six moments of the straight-line fit n = s c + b.  n_img, c_img [n_pixels] float32; mask
+ *       [n_pixels] uint8 or NULL (non-zero excludes).  A pixel counts when n and c are finite, mask == 0 and lo <= r <= hi
+ *       (inclusive) with r = double(n) - (s double(c) + b), the product, the sum and the difference each rounded; lo = -inf,
+ *       hi = +inf keeps every finite unmasked pair.  out6 [6] float64 on the device = count, sum c, sum n, sum c c, sum c n,
+ *       sum n n (terms formed in float64).  The count is an exact 64-bit integer, written as a double.  The sums are formed per
+ *       lane, per workgroup and over the workgroups in an order that depends on n_pixels alone (no floating-point atomics): the
+ *       same input gives the same bits on every run and for every alignment.  s, b, lo, hi must not be NaN.  ws: a workspace of
+ *       apgpu_pair_moments_ws_bytes(n_pixels) bytes, 8-byte aligned, owned by the caller; one launch.
+ *
+ *     apgpu_linear_combine_f32: out = (float32(ca x) + float32(cb y)) + c0, every operation in float32, NaN (0x7fc00000) where x
+ *       or y is not finite; y NULL: out = float32(ca x) + c0, NaN where x is not finite.  out may be x or y.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_BLUR_MAX_RADIUS 32
+#define APGPU_BLUR_TILE_H 32
+#define APGPU_BLUR_TILE_W 64
+int apgpu_gauss_blur_norm_f32(const float *data, int64_t height, int64_t width, const double *taps_host, int32_t radius,
+                              double min_weight, float *out, void *stream);
+size_t apgpu_pair_moments_ws_bytes(int64_t n_pixels);
+int apgpu_pair_moments_f64(const float *n_img, const float *c_img, const uint8_t *mask, int64_t n_pixels, double s, double b,
+                           double lo, double hi, double *out6, void *ws, size_t ws_bytes, void *stream);
+int apgpu_linear_combine_f32(const float *x, const float *y, float ca, float cb, float c0, float *out, int64_t n_pixels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
