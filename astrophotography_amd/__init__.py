@@ -27,6 +27,7 @@ _LAZY = {
     'ApComposite': ('.core.ApComposite', 'ApComposite'),
     'ApDebayer': ('.core.ApDebayer', 'ApDebayer'),
     'ApContinuumSubtract': ('.core.ApContinuumSubtract', 'ApContinuumSubtract'),
+    'ApDeconvolve': ('.core.ApDeconvolve', 'ApDeconvolve'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

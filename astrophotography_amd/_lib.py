@@ -23,6 +23,7 @@ GAUSS2D_REC, GAUSS2D_MAX_BOX = 20, 76                   # APGPU_GAUSS2D_REC, APG
 REGISTER_MAX_K, REGISTER_MAX_STARS = 64, 4096           # APGPU_REGISTER_MAX_K, APGPU_REGISTER_MAX_STARS
 COMPOSITE_MAX_VARIANTS, TONE_TABLE_LEN = 16, 10241      # APGPU_COMPOSITE_MAX_VARIANTS, APGPU_TONE_TABLE_LEN
 BLUR_MAX_RADIUS, BLUR_TILE_H, BLUR_TILE_W = 32, 32, 64  # APGPU_BLUR_MAX_RADIUS, APGPU_BLUR_TILE_H, APGPU_BLUR_TILE_W
+DECONV_MAX_RADIUS, DECONV_TILE_H, DECONV_TILE_W = 12, 32, 64    # APGPU_DECONV_MAX_RADIUS, APGPU_DECONV_TILE_H, APGPU_DECONV_TILE_W
 
 
 class ApGpuError(RuntimeError):
@@ -148,6 +149,15 @@ SIGNATURES = {
     'apgpu_pair_moments_f64': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double,
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'apgpu_linear_combine_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
+    'apgpu_deconv_ws_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'apgpu_deconv_norm_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    'apgpu_deconv_ratio_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'apgpu_deconv_update_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_void_p,
+                                          C.c_void_p]),
+    'apgpu_richardson_lucy_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, C.c_float,
+                                            C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p]),
 }
 
 _lib = None

@@ -2133,3 +2133,160 @@ def psf_match(n, c, fwhm_n, fwhm_c, threshold=0.05, min_weight=0.5):
     if sn < sc:
         return gauss_blur(n, taps, min_weight), c, dict(blurred='narrow', sigma_k=sigma_k, taps=taps)
     return n, gauss_blur(c, taps, min_weight), dict(blurred='continuum', sigma_k=sigma_k, taps=taps)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F12: ApDeconvolve - damped Richardson-Lucy deconvolution with the image's own PSF (csrc/deconvolve.hip; the
+# reference has no such stage: the arithmetic is this project's definition, include/apgpu.h F12, tests/deconvolve_model.py)
+DECONV_MAX_RADIUS = _lib.DECONV_MAX_RADIUS
+
+
+def _psf_sampled(profile, fwhm, radius, default_radius):
+    import math
+    fwhm = float(fwhm)
+    if not (fwhm > 0.0 and math.isfinite(fwhm)):
+        raise ValueError('the FWHM must be finite and > 0, got %r' % fwhm)
+    R = int(default_radius if radius is None else radius)
+    if R < 0 or R > DECONV_MAX_RADIUS:
+        raise ValueError('a PSF of FWHM %g pixels needs a radius of %d, the kernels hold %d: bin the image' % (fwhm, R, DECONV_MAX_RADIUS))
+    k = np.arange(2 * R + 1, dtype=np.float64) - R
+    sub = (np.arange(5, dtype=np.float64) + 0.5) / 5.0 - 0.5             # 5 x 5 midpoints inside the pixel
+    g = np.zeros((2 * R + 1, 2 * R + 1), np.float64)
+    for dy in sub:
+        for dx in sub:
+            g += profile((k[:, None] + dy) ** 2 + (k[None, :] + dx) ** 2)
+    return (g / g.sum()).astype(np.float32)
+
+
+def psf_gaussian(fwhm, radius=None):
+    """float32 [K][K], K = 2 radius + 1: a round Gaussian of the given FWHM (pixels), pixel-integrated by 5 x 5 midpoint sub-sampling
+    in float64, normalised to sum 1, then cast.  radius: ceil(1.7 FWHM) unless given; above 12 raises ValueError."""
+    import math
+    s = float(fwhm) * FWHM_TO_SIGMA
+    return _psf_sampled(lambda r2: np.exp(-r2 / (2.0 * s * s)), fwhm, radius, math.ceil(1.7 * float(fwhm)))
+
+
+def psf_moffat(fwhm, beta=2.5, radius=None):
+    """The same for a Moffat profile (1 + r^2 / alpha^2)^-beta with alpha = FWHM / (2 sqrt(2^(1/beta) - 1)).  radius: ceil(2.5 FWHM)
+    unless given; above 12 raises ValueError."""
+    import math
+    beta = float(beta)
+    if not (beta > 1.0 and math.isfinite(beta)):
+        raise ValueError('the Moffat beta must be finite and > 1, got %r' % beta)
+    alpha = float(fwhm) / (2.0 * math.sqrt(2.0 ** (1.0 / beta) - 1.0))
+    return _psf_sampled(lambda r2: (1.0 + r2 / (alpha * alpha)) ** -beta, fwhm, radius, math.ceil(2.5 * float(fwhm)))
+
+
+def psf_stamp(psf):
+    """(contiguous float32 [K][K] host array, radius) of a PSF stamp given as an array or tensor; the weights are taken as they are.
+    ValueError for a shape that is not odd and square, a radius above 12, a negative or non-finite weight or a sum <= 0."""
+    p = np.ascontiguousarray(psf.cpu().numpy() if hasattr(psf, 'cpu') else psf, dtype=np.float32)
+    if p.ndim != 2 or p.shape[0] != p.shape[1] or p.shape[0] % 2 != 1:
+        raise ValueError('the PSF stamp must be square with an odd side, got shape %s' % (p.shape,))
+    R = p.shape[0] // 2
+    if R > DECONV_MAX_RADIUS:
+        raise ValueError('a PSF stamp of radius %d, the kernels hold %d: bin the image' % (R, DECONV_MAX_RADIUS))
+    if not np.all(np.isfinite(p)) or np.any(p < 0) or not p.astype(np.float64).sum() > 0:
+        raise ValueError('the PSF weights must be finite and >= 0 with a sum > 0')
+    return p, R
+
+
+def _psf_arg(p):
+    return p.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _deconv_plane(t, name, like):
+    t = _image_f32(t, name)
+    if tuple(t.shape) != tuple(like.shape):
+        raise ValueError('%s must have the image shape %s, got %s' % (name, tuple(like.shape), tuple(t.shape)))
+    return t
+
+
+def _deconv_out(out, like, *distinct):
+    if out is None:
+        return torch.empty_like(like)
+    _need_cuda(out)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(like.shape) or not out.is_contiguous() or \
+            any(out.data_ptr() == t.data_ptr() for t in distinct):
+        raise ValueError('out must be a contiguous float32 device tensor of the image shape, distinct from the plane under the taps')
+    return out
+
+
+def deconv_norm(data, psf, min_weight=0.1, out=None):
+    """Step 1 of F12: inv = 1 / n where n = sum p W >= min_weight (W = 1 at the finite pixels), else 0."""
+    data = _image_f32(data)
+    p, R = psf_stamp(psf)
+    out = _deconv_out(out, data, data)
+    check(_lib.load().apgpu_deconv_norm_f32(_ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(min_weight), _ptr(out), _stream()))
+    return out
+
+
+def deconv_ratio(u, data, psf, sky, gain=1.0, readnoise=0.0, damp=0.0, out=None):
+    """Step 3 of F12: the forward convolution of u (edges replicated) plus the sky, and the (damped) ratio against the data."""
+    data = _image_f32(data)
+    u = _deconv_plane(u, 'u', data)
+    p, R = psf_stamp(psf)
+    out = _deconv_out(out, data, u)
+    check(_lib.load().apgpu_deconv_ratio_f32(_ptr(u), _ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(sky), float(gain),
+                                             float(readnoise), float(damp), _ptr(out), _stream()))
+    return out
+
+
+def deconv_update(u, ratio, inv, psf, out=None):
+    """Step 4 of F12: u' = (u q) inv where inv != 0, else u, with q the back-projection (correlation) of the ratio plane."""
+    u = _image_f32(u, 'u')
+    ratio, inv = _deconv_plane(ratio, 'ratio', u), _deconv_plane(inv, 'inv', u)
+    p, R = psf_stamp(psf)
+    out = _deconv_out(out, u, ratio)
+    check(_lib.load().apgpu_deconv_update_f32(_ptr(u), _ptr(ratio), _ptr(inv), u.shape[0], u.shape[1], _psf_arg(p), R, _ptr(out), _stream()))
+    return out
+
+
+def deconv_workspace(shape, device):
+    """A workspace for richardson_lucy on images of this shape (16 bytes per pixel: the ratio, the norm and two estimates)."""
+    return torch.empty(_lib.load().apgpu_deconv_ws_bytes(int(shape[0]), int(shape[1])), dtype=torch.uint8, device=device)
+
+
+def richardson_lucy(data, psf, sky, niter=30, damp=0.0, gain=1.0, readnoise=0.0, start=None, min_weight=0.1, ws=None, out=None):
+    """Damped Richardson-Lucy deconvolution of a float32 image [H, W] whose non-finite pixels mean "no data" (include/apgpu.h F12;
+    tests/deconvolve_model.py).  psf: an odd, square stamp of radius <= 12, its weights used as given.  sky: the level (ADU) that is
+    not deconvolved.  damp: White's threshold T in sigma (0: plain RL); gain (e-/ADU) and readnoise (ADU) give the variance it is
+    measured in.  start: a positive scalar, a plane of the image shape, or None: the float64 mean of data - sky over the valid
+    pixels, at least 1e-6.  ws: a uint8 device workspace (deconv_workspace) or None; out: the output tensor or None.  1 + 2 niter
+    launches on the current stream, nothing else inside the loop.
+
+    Returns (image, report): the image is the estimate plus the sky, NaN where the input has no data; report['start'] is the start
+    level that was used (a float32 value, None for a plane)."""
+    import math
+    data = _image_f32(data)
+    p, R = psf_stamp(psf)
+    niter = int(niter)
+    if niter < 0:
+        raise ValueError('niter must be >= 0, got %d' % niter)
+    plane, level = None, None
+    if start is not None and np.ndim(start) != 0:
+        plane = _deconv_plane(start, 'start', data)
+    else:
+        if start is None:
+            ok = torch.isfinite(data)
+            cnt = int(ok.sum().item())
+            mean = float(torch.where(ok, data.to(torch.float64) - float(np.float32(sky)), 0.0).sum().item()) / cnt if cnt else 0.0
+            start = max(mean, 1e-6)
+        level = float(np.float32(start))
+        if not (level > 0.0 and math.isfinite(level)):
+            raise ValueError('the start level must be finite and > 0, got %r' % (start,))
+    out = _deconv_out(out, data, data, *(() if plane is None else (plane,)))
+    lib = _lib.load()
+    need = lib.apgpu_deconv_ws_bytes(data.shape[0], data.shape[1])
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=data.device)
+    else:
+        _need_cuda(ws)
+        if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
+            raise ValueError('ws must be a contiguous, 16-byte aligned uint8 device tensor of at least %d bytes (ops.deconv_workspace)' % need)
+    check(lib.apgpu_richardson_lucy_f32(_ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(sky), float(gain), float(readnoise),
+                                        float(damp), niter, 0.0 if level is None else level, _ptr(plane), float(min_weight), _ptr(out),
+                                        _ptr(ws), ws.numel(), _stream()))
+    report = dict(start=level, niter=niter, radius=R, damp=float(damp), sky=float(np.float32(sky)), gain=float(gain), readnoise=float(readnoise),
+                  min_weight=float(min_weight), launches=1 + 2 * niter)
+    return out, report

@@ -727,6 +727,56 @@ int apgpu_pair_moments_f64(const float *n_img, const float *c_img, const uint8_t
                            double lo, double hi, double *out6, void *ws, size_t ws_bytes, void *stream);
 int apgpu_linear_combine_f32(const float *x, const float *y, float ca, float cb, float c0, float *out, int64_t n_pixels, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F12 ApDeconvolve: damped Richardson-Lucy deconvolution of a co-add with its own PSF.  The reference has no such stage, so the
+ *     arithmetic is this project's own definition, restated in tests/deconvolve_model.py.
+ *
+ *     Inputs.  d [height][width] float32; a non-finite value means "no data"; valid(y, x) = inside the image and finite.
+ *       p [K][K] float32 on the HOST, K = 2 R + 1, 0 <= R <= APGPU_DECONV_MAX_RADIUS (larger: APGPU_EUNSUPPORTED); every weight
+ *       finite and >= 0, the sum > 0; the weights are used as given (the host normalises them).  Sky level b >= 0; gain > 0
+ *       (e-/ADU); read noise rn >= 0 (ADU); damping threshold T >= 0; niter >= 0; min_weight >= 0 (0.1 by default in ops).
+ *     Rounding and order.  Every operation is float32 and every multiply and add rounds on its own (no contraction, no fmaf).
+ *       Accumulators start at +0.  The 2-D tap order is row-major: j (PSF row) ascending outside, i ascending inside.
+ *       min(x, 1) means x where x < 1, else 1, and max(x, 0) means x where x > 0, else 0 (a NaN gives the constant).
+ *     1 Norm plane (once): n(y, x) = sum_{j,i} p[j][i] W(y + j - R, x + i - R), W = 1 where valid and 0 elsewhere, outside the
+ *       image included.  inv(y, x) = 1 / n where n >= min_weight, else 0.
+ *     2 Start: u(y, x) = start_level everywhere (a positive float32), or the caller's start plane.
+ *     3 Forward + ratio, per iteration: c = (sum_{j,i} p[j][i] u(clampy(y + R - j), clampx(x + R - i))) + b: a true convolution
+ *       (the PSF flipped), u edge-replicated outside the image.  At an invalid pixel r = 0.  At a valid pixel with !(c > 0), r = 1.
+ *       Otherwise, with T == 0: r = d / c (IEEE division).  Otherwise, with T > 0: e = d - c; var = max(c, 0) / gain + rn rn;
+ *       U = min((e e) / ((T T) var), 1); U2 = U U; U4 = U2 U2; U8 = U4 U4; U9 = U8 U; w = U9 (10 - 9 U); r = 1 + (w e) / c.
+ *       In both cases r = max(r, 0).  (White's damped RL with the Gaussian form of the likelihood ratio: no log.)
+ *     4 Back-projection + update: q = sum_{j,i} p[j][i] r(y + j - R, x + i - R), a correlation; taps outside the image are +0.
+ *       u' = (u q) inv where inv != 0, else u' = u.
+ *     5 Output: out = u + b at the valid pixels, NaN (0x7fc00000) at the others: holes keep their footprint.
+ *
+ *     apgpu_deconv_norm_f32 (step 1), apgpu_deconv_ratio_f32 (step 3) and apgpu_deconv_update_f32 (step 4) are the steps alone, one
+ *       launch each; all planes [height][width] float32 on the device, 4-byte aligned; the output plane must not be the plane the
+ *       taps read (data, u and ratio respectively).
+ *     apgpu_richardson_lucy_f32 enqueues 1 + 2 niter launches and nothing else (no allocation, no host synchronisation):
+ *       the norm launch also writes the start into the first u plane (or, with niter = 0, the output), u ping-pongs between two
+ *       planes, and the last update writes out = u + b / NaN directly.  start_plane NULL: u = start_level (finite, > 0).  ws: a
+ *       workspace of apgpu_deconv_ws_bytes(height, width) bytes (the ratio, inv and two u planes, 16 bytes per pixel), 16-byte
+ *       aligned, owned by the caller.  out must be neither data nor the start plane.
+ *     APGPU_EINVAL: a NULL plane, a negative or non-finite weight, a PSF sum <= 0, sky, gain, read noise or damp out of range, a
+ *       workspace that is too small.
+ *     A workgroup owns a tile of APGPU_DECONV_TILE_H x APGPU_DECONV_TILE_W outputs and stages it with a halo of R in LDS by the
+ *       rule of its pass, so image edges and tile edges take one path (csrc/deconvolve.hip).
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_DECONV_MAX_RADIUS 12
+#define APGPU_DECONV_TILE_H 32
+#define APGPU_DECONV_TILE_W 64
+size_t apgpu_deconv_ws_bytes(int64_t height, int64_t width);
+int apgpu_deconv_norm_f32(const float *data, int64_t height, int64_t width, const float *psf_host, int32_t radius, float min_weight,
+                          float *inv, void *stream);
+int apgpu_deconv_ratio_f32(const float *u, const float *data, int64_t height, int64_t width, const float *psf_host, int32_t radius,
+                           float sky, float gain, float readnoise, float damp, float *ratio, void *stream);
+int apgpu_deconv_update_f32(const float *u, const float *ratio, const float *inv, int64_t height, int64_t width, const float *psf_host,
+                            int32_t radius, float *u_out, void *stream);
+int apgpu_richardson_lucy_f32(const float *data, int64_t height, int64_t width, const float *psf_host, int32_t radius, float sky, float gain,
+                              float readnoise, float damp, int32_t niter, float start_level, const float *start_plane, float min_weight,
+                              float *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
