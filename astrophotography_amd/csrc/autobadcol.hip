@@ -18,12 +18,12 @@
 //    are widened to float64 as they are loaded (numpy's median of integers is float64).
 // 2. sliding_stats_kernel<T>: one lane per output index.  The lane compacts its window's finite values, in order, into
 //    its slot of the workspace and runs astropy's noaxis clip on them with sigclip_global.hip's definitions: median by
-//    exact selection, numpy's pairwise summation tree (8 accumulators per 128-element leaf, halves rounded down to a
-//    multiple of 8 above that), np.var's float32 mean T(sum) / T(n), var T(float64(s2) / n), mean T(float64(sum) / n),
-//    float64 bounds demoted to T for the comparison.  The default window (11) keeps everything in one lane; any
-//    window_len >= 1 works (long windows are slow but exact).
+//    exact selection, numpy's summation order (np_exact.h), np.var's float32 mean T(sum) / T(n), var T(float64(s2) / n),
+//    mean T(float64(sum) / n), float64 bounds demoted to T for the comparison.  The default window (11) keeps everything
+//    in one lane; any window_len >= 1 works (long windows are slow but exact).
 // Both kernels run on the caller's stream with no host synchronisation; the host reads back only the per-line results.
 #include "common.h"
+#include "np_exact.h"
 
 namespace {
 using namespace apgpu;
@@ -35,42 +35,12 @@ constexpr int kDigitBits = 8;
 constexpr int kDigitBins = 1 << kDigitBits;
 constexpr long long kMaPathLen = 600;         // numpy _nanmedian: a.shape[axis] < 600 -> _nanmedian_small (np.ma.median)
 
-template <typename T> struct Key;
-template <> struct Key<float> {
-    using U = unsigned;
-    static constexpr int bits = 32;
-    __device__ static U to(float x)
-    {
-        const unsigned b = __float_as_uint(x);
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    __device__ static float from(U k)
-    {
-        const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        return __uint_as_float(b);
-    }
-};
-template <> struct Key<double> {
-    using U = unsigned long long;
-    static constexpr int bits = 64;
-    __device__ static U to(double x)
-    {
-        const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    }
-    __device__ static double from(U k)
-    {
-        const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-        return __longlong_as_double((long long)b);
-    }
-};
-
 // ---- 1. axis medians ---------------------------------------------------------------------------------------------------
 // Per-line selection state, in LDS.
 template <typename T>
 struct LineSel {
-    typename Key<T>::U prefix;        // key bits found so far (upper middle element, rank k of the non-NaN values)
-    typename Key<T>::U below;         // largest key below the final key (even count, found by the extra pass)
+    typename OrderKey<T>::U prefix;        // key bits found so far (upper middle element, rank k of the non-NaN values)
+    typename OrderKey<T>::U below;         // largest key below the final key (even count, found by the extra pass)
     long long n;                      // non-NaN values
     long long k;                      // rank still searched inside the current prefix
     int need_below;                   // even count whose lower middle element is not fixed by the histograms
@@ -81,7 +51,7 @@ struct LineSel {
 template <typename In, typename T, bool COLS>
 __global__ __launch_bounds__(COLS ? kColBlock : kMedBlock) void axis_median_kernel(const In *__restrict__ data, long long H, long long W, T *__restrict__ out)
 {
-    using K = Key<T>;
+    using K = OrderKey<T>;
     using U = typename K::U;
     constexpr int levels = K::bits / kDigitBits;
     constexpr int BS = COLS ? kColBlock : kMedBlock;
@@ -190,102 +160,41 @@ __global__ __launch_bounds__(COLS ? kColBlock : kMedBlock) void axis_median_kern
 }
 
 // ---- 2. sliding clipped statistics ---------------------------------------------------------------------------------------
-template <int SQ, typename T>
-__device__ __forceinline__ T term(T x, T mean)
+// the terms of numpy's two sums: the values, and their squared deviations from the mean
+template <typename T>
+struct Values {
+    const T *a;
+    __device__ T operator()(long long i) const { return a[i]; }
+};
+template <typename T>
+struct SquaredDev {
+    const T *a;
+    T mean;
+    __device__ T operator()(long long i) const { const T d = a[i] - mean; return d * d; }
+};
+
+// np.add.reduce of the terms f(0) .. f(n - 1) (csrc/np_exact.h) by this lane, its stack private: every lane runs a sum of
+// its own.  Out of line, so that the common short windows below do not carry the tree's registers.
+template <typename T, typename F>
+__device__ __noinline__ T numpy_tree_sum(long long n, F f)
 {
-    if constexpr (SQ) { const T d = x - mean; return d * d; }
-    else return x;
+    NpSumStack<T> st;
+    return np_add_reduce<T>(n, f, st);
 }
 
-// numpy pairwise_sum of a leaf (n <= 128)
-template <int SQ, typename T>
-__device__ T leaf_sum(const T *a, long long n, T mean)
+// windows of up to 128 values (the default 11 among them) are one leaf and stay in registers
+template <typename T, typename F>
+__device__ __forceinline__ T numpy_sum(long long n, F f)
 {
-    if (n < 8) {
-        T res = (T)0;
-        for (long long i = 0; i < n; i++) res = res + term<SQ, T>(a[i], mean);
-        return res;
-    }
-    T r[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = term<SQ, T>(a[k], mean);
-    long long i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) r[k] = r[k] + term<SQ, T>(a[i + k], mean);
-    }
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res = res + term<SQ, T>(a[i], mean);
-    return res;
-}
-
-// numpy's np.add.reduce of a contiguous 1-D array: 8192-element pieces folded in order, each piece a pairwise tree
-// (split n / 2 rounded down to a multiple of 8, leaves of <= 128).  The recursion runs on an explicit stack: a piece
-// has at most 7 levels above its leaves (8192 -> 128 halves 6 times).
-template <int SQ, typename T>
-__device__ __noinline__ T numpy_tree_sum(const T *a, long long n, T mean)
-{
-    T total = (T)0;
-    for (long long p0 = 0; p0 < n; p0 += 8192) {
-        const long long pn = (n - p0) < 8192 ? (n - p0) : 8192;
-        // stack of pending nodes (offset, count) and of partial sums waiting for their right halves
-        long long st_off[8], st_n[8];
-        T acc[8];
-        int acc_state[8];                      // 0: left half pending, 1: left half done (acc holds it)
-        int sp = 0;
-        st_off[0] = p0; st_n[0] = pn; acc_state[0] = 0;
-        T val = (T)0;
-        bool have = false;
-        // iterative post-order walk
-        while (true) {
-            if (!have) {
-                const long long off = st_off[sp], cnt = st_n[sp];
-                if (cnt <= 128) {
-                    val = leaf_sum<SQ, T>(a + off, cnt, mean);
-                    have = true;
-                } else {
-                    long long n2 = cnt / 2;
-                    n2 -= n2 % 8;
-                    acc_state[sp] = 0;
-                    // descend into the left half
-                    st_off[sp + 1] = off; st_n[sp + 1] = n2; acc_state[sp + 1] = 0;
-                    sp++;
-                    continue;
-                }
-            }
-            // `val` is the sum of node sp: hand it to its parent
-            if (sp == 0) break;
-            const int par = sp - 1;
-            if (acc_state[par] == 0) {
-                acc[par] = val;
-                acc_state[par] = 1;
-                long long n2 = st_n[par] / 2;
-                n2 -= n2 % 8;
-                st_off[sp] = st_off[par] + n2; st_n[sp] = st_n[par] - n2; acc_state[sp] = 0;
-                have = false;                  // now the right half
-            } else {
-                val = acc[par] + val;
-                sp = par;                      // node par is complete
-            }
-        }
-        total = total + val;
-    }
-    return total;
-}
-
-// np.add.reduce; windows of up to 128 values (the default 11 among them) are one leaf and stay in registers
-template <int SQ, typename T>
-__device__ __forceinline__ T numpy_sum(const T *a, long long n, T mean)
-{
-    if (n <= 128) return (T)0 + leaf_sum<SQ, T>(a, n, mean);
-    return numpy_tree_sum<SQ, T>(a, n, mean);
+    if (n <= 128) return (T)0 + np_leaf_sum<T>((int)n, f);
+    return numpy_tree_sum<T>(n, f);
 }
 
 // k-th smallest (0-based) of a[0 .. n) by bitwise search on the order-preserving keys (no reordering of a)
 template <typename T>
-__device__ typename Key<T>::U select_key(const T *a, long long n, long long k)
+__device__ typename OrderKey<T>::U select_key(const T *a, long long n, long long k)
 {
-    using K = Key<T>;
+    using K = OrderKey<T>;
     using U = typename K::U;
     if (n <= 24) {                              // rank counting: n^2 compares, cheaper than `bits` passes for short windows
         for (long long i = 0; i < n; i++) {
@@ -314,7 +223,7 @@ __device__ typename Key<T>::U select_key(const T *a, long long n, long long k)
 template <typename T>
 __device__ T median_of(const T *a, long long n)
 {
-    using K = Key<T>;
+    using K = OrderKey<T>;
     const T hi = K::from(select_key<T>(a, n, n / 2));
     if (n & 1) return hi;
     const T lo = K::from(select_key<T>(a, n, n / 2 - 1));
@@ -326,7 +235,7 @@ template <typename T>
 __device__ T std_of(const T *a, long long n, T sum)
 {
     const T mean = sum / (T)n;
-    const T s2 = numpy_sum<1, T>(a, n, mean);
+    const T s2 = numpy_sum<T>(n, SquaredDev<T>{a, mean});
     const T var = (T)((double)s2 / (double)n);
     return (T)sqrt((double)var);
 }
@@ -349,12 +258,12 @@ __global__ __launch_bounds__(kMedBlock) void sliding_stats_kernel(const T *__res
         long long n = 0;
         for (long long j = a; j < b; j++) {
             const T x = m[j];
-            if (fabs((double)x) < __builtin_inf()) buf[n++] = x;            // finite values, in order
+            if (is_finite(x)) buf[n++] = x;                                 // finite values, in order
         }
         // astropy _sigmaclip_noaxis: while something was removed and iteration < maxiters
         for (int it = 0; n > 0 && (maxiters < 0 || it < maxiters); it++) {
             const T med = median_of<T>(buf, n);
-            const T sd = std_of<T>(buf, n, numpy_sum<0, T>(buf, n, (T)0));
+            const T sd = std_of<T>(buf, n, numpy_sum<T>(n, Values<T>{buf}));
             // SigmaClip._compute_bounds: T scalars * python float -> float64, demoted to T for the comparison
             const T lo = (T)((double)med - (double)sd * sigma), hi = (T)((double)med + (double)sd * sigma);
             long long k = 0;
@@ -368,7 +277,7 @@ __global__ __launch_bounds__(kMedBlock) void sliding_stats_kernel(const T *__res
         }
         double mean = __builtin_nan(""), sd = __builtin_nan("");
         if (n > 0) {
-            const T sum = numpy_sum<0, T>(buf, n, (T)0);
+            const T sum = numpy_sum<T>(n, Values<T>{buf});
             mean = (double)(T)((double)sum / (double)n);                    // np.mean: T(float64(sum) / n)
             sd = (double)std_of<T>(buf, n, sum);
         }

@@ -10,6 +10,7 @@
 // cubic B-spline evaluation of the mesh over every pixel.  The mesh-sized steps between them (ny x nx numbers: filling
 // excluded boxes, the 3 x 3 median filter, the spline prefilter) are host logic in core/ApMeasureBackground.py.
 #include "common.h"
+#include "np_exact.h"
 
 namespace {
 using namespace apgpu;
@@ -136,18 +137,6 @@ __global__ __launch_bounds__(kBlock) void dilate_kernel(const uint8_t *__restric
 // pixels count as masked.  Output per box (float64): median, std of the final survivors, number of survivors,
 // number of masked pixels before clipping.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned f32_key(float x)
-{
-    const unsigned u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_f32(unsigned k)
-{
-    const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
-
 struct BoxView {
     const float *data;
     const uint8_t *mask;
@@ -162,7 +151,7 @@ __device__ __forceinline__ float box_value(const BoxView &b, int e)
     const int64_t p = (int64_t)rr * b.W + cc;
     if (b.mask && b.mask[p]) return __builtin_nanf("");
     const float x = b.data[p];
-    return (fabsf(x) < __builtin_inff()) ? x : __builtin_nanf("");
+    return is_finite(x) ? x : __builtin_nanf("");
 }
 
 template <int NT>
@@ -353,7 +342,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
                 if (x >= lo && x <= hi) {
                     const double d = mean - (double)x;
                     ss += d * d;
-                    const unsigned dg = f32_key(x) >> (32 - kBoxDigit);
+                    const unsigned dg = OrderKey<float>::to(x) >> (32 - kBoxDigit);
                     if (dg != cur_d) {
                         if (cur_d != kNoDigit) atomicAdd(&hist[cur_d], cur_n);
                         cur_d = dg;
@@ -371,7 +360,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
             zero_hist();
             for_each([&](float x) {
                 if (x >= lo && x <= hi) {
-                    const unsigned key = f32_key(x);
+                    const unsigned key = OrderKey<float>::to(x);
                     if ((key >> 21) == prefix) atomicAdd(&hist[(key >> 10) & (kBoxBins - 1)], 1u);
                 }
             });
@@ -397,7 +386,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
                     const double d = (double)x - p;
                     s1 += d;
                     s2 = fma(d, d, s2);
-                    const unsigned key = f32_key(x);
+                    const unsigned key = OrderKey<float>::to(x);
                     const unsigned dg = key >> (32 - kBoxDigit);
                     if (dg != cur_d) {
                         if (cur_d != kNoDigit) atomicAdd(&hist[cur_d], cur_n);
@@ -440,7 +429,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
                 zero_hist();
                 for_each([&](float x) {
                     if (x >= lo && x <= hi) {
-                        const unsigned key = f32_key(x);
+                        const unsigned key = OrderKey<float>::to(x);
                         if ((key >> 21) == prefix) atomicAdd(&hist[(key >> 10) & (kBoxBins - 1)], 1u);
                     }
                 });
@@ -455,7 +444,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
         unsigned below = 0;
         for_each([&](float x) {
             if (x >= lo && x <= hi) {
-                const unsigned key = f32_key(x);
+                const unsigned key = OrderKey<float>::to(x);
                 const unsigned top = key >> 10;
                 if (top == prefix) atomicAdd(&hist[key & 1023u], 1u);
                 else if (top < prefix) below = key > below ? key : below;
@@ -479,7 +468,7 @@ __global__ __launch_bounds__(NT) void box_stats_kernel(const float *__restrict__
                 key1 = mx;
             }
         }
-        med = ((double)key_f32(key1) + (double)key_f32(key2)) / 2.0;
+        med = ((double)OrderKey<float>::from(key1) + (double)OrderKey<float>::from(key2)) / 2.0;
         if (final_pass) break;
         const double lo64 = med - sigma * sd, hi64 = med + sigma * sd;
         float lof = (float)lo64, hif = (float)hi64;

@@ -4,7 +4,7 @@
 // UNPINNED), restated in tests/composite_model.py.  Everything is float32 in the stated order, no contraction.
 //
 //   levels     v = the finite values of a channel in ascending order; level(q) = v[floor(q (n - 1))]: an exact order
-//              statistic by radix select on the order-preserving key of the float (KeyOf<float> of sigclip_global.hip), 8-bit
+//              statistic by radix select on the order-preserving key of the float (OrderKey<float> of np_exact.h), 8-bit
 //              digits, four levels.  All three channels and both targets (min, max) go through the same four reads of
 //              the planes; the digit of each target is picked on the device by a one-workgroup kernel between them.
 //   composite  scale_c = 1 / (hi_c - lo_c)                     (0 unless hi_c > lo_c)
@@ -18,6 +18,7 @@
 //              One pass: a lane reads four consecutive pixels of the three planes once and writes them for every variant
 //              (a variant = a table and a saturation), as 3 or 6 whole dwords where the destination is dword aligned.
 #include "common.h"
+#include "np_exact.h"
 
 namespace apgpu {
 namespace {
@@ -41,19 +42,6 @@ struct LevelState {
     unsigned hist[3][2][kLevBins];
 };
 
-__device__ __forceinline__ unsigned key_of(float x)
-{
-    const unsigned b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float value_of(unsigned k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-__device__ __forceinline__ bool finite_bits(unsigned b) { return (b & 0x7f800000u) != 0x7f800000u; }
-
 // One level of the select: the histogram of the digit at `shift` over the finite values whose higher key bits equal the
 // target's prefix.  blockIdx.y = channel.  On the first level the prefix is empty and both targets share histogram 0.
 // A lane's consecutive equal digits are added in one LDS atomic (sky pixels share their leading digits).
@@ -70,9 +58,8 @@ __global__ __launch_bounds__(kLevBlock) void level_hist_kernel(const float *__re
     __syncthreads();
     unsigned cur_d[2] = {kNoDigit, kNoDigit}, cur_n[2] = {0, 0};
     auto add = [&](float x) {
-        const unsigned b = __float_as_uint(x);
-        if (!finite_bits(b)) return;
-        const unsigned key = key_of(x);
+        if (!is_finite(x)) return;
+        const unsigned key = OrderKey<float>::to(x);
         const unsigned d = (key >> shift) & (kLevBins - 1);
         const unsigned top = pass == 0 ? 0u : key >> (shift + kLevDigit);
 #pragma unroll
@@ -164,7 +151,7 @@ __global__ __launch_bounds__(6 * kWave) void level_pick_kernel(LevelState *__res
         if (pass == 0 && t == 0) st->n[c] = n;
         if (pass == kLevPasses - 1) {
             const float m = manual ? manual[2 * c + t] : __builtin_nanf("");
-            levels[2 * c + t] = m == m ? m : value_of(prefix);
+            levels[2 * c + t] = m == m ? m : OrderKey<float>::from(prefix);
         }
     }
     if (n == 0 && lane == 0) {
@@ -204,7 +191,7 @@ struct PixelCommon {
 __device__ __forceinline__ PixelCommon pixel_common(const float (&x)[3], const float (&lo)[3], const float (&scale)[3])
 {
     PixelCommon p;
-    p.black = !(finite_bits(__float_as_uint(x[0])) && finite_bits(__float_as_uint(x[1])) && finite_bits(__float_as_uint(x[2])));
+    p.black = !(is_finite(x[0]) && is_finite(x[1]) && is_finite(x[2]));
 #pragma unroll
     for (int c = 0; c < 3; c++) p.s[c] = pos((x[c] - lo[c]) * scale[c]);
     p.y = ((p.s[0] + p.s[1]) + p.s[2]) * (float)(1.0 / 3.0);

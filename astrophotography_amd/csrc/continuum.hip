@@ -21,6 +21,7 @@
 // consecutive) and writes the image.  The kernel is instantiated for R <= 4, 8, 16 and 32: the LDS of an instance is
 // (32 + 2 RMAX) (68 + 2 RMAX) 4 + (32 + 2 RMAX) 64 16 bytes, 149 KiB of the 160 KiB of a CU for RMAX = 32 and 52 KiB for RMAX = 4.
 #include "common.h"
+#include "np_exact.h"
 
 namespace apgpu {
 namespace {
@@ -33,8 +34,6 @@ static_assert(kTileW == kWave, "a wavefront owns one tile row");
 struct BlurTaps {
     double w[2 * kMaxR + 1];
 };
-
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 template <int RMAX>
 __global__ __launch_bounds__(kBlock) void gauss_blur_kernel(const float *__restrict__ data, long long H, long long W, const BlurTaps taps, int R,
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void gauss_blur_kernel(const float *__restr
             for (int k = 0; k <= 2 * R; k++) {
                 const float v = p[k];
                 const double w = wt[k];
-                const bool ok = finite_f32(v);
+                const bool ok = is_finite(v);
                 const double t = w * (double)v;
                 a = ok ? a + t : a;
                 m = ok ? m + w : m;
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void gauss_blur_kernel(const float *__restr
             M = M + w * q.y;
         }
         const float c = tile[ly + R][off + R + lane];
-        const bool ok = finite_f32(c) && M >= min_weight;
+        const bool ok = is_finite(c) && M >= min_weight;
         out[(size_t)gy * (size_t)W + (size_t)(tx0 + lane)] = ok ? (float)(A / M) : nanv;
     }
 }
@@ -124,7 +123,7 @@ struct Moments {
 
 __device__ __forceinline__ void moments_add(Moments &t, float nv, float cv, unsigned mk, double s, double b, double lo, double hi)
 {
-    if (mk != 0 || !finite_f32(nv) || !finite_f32(cv)) return;
+    if (mk != 0 || !is_finite(nv) || !is_finite(cv)) return;
     const double y = (double)nv, c = (double)cv;
     const double r = y - (s * c + b);
     if (!(r >= lo && r <= hi)) return;
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void pair_moments_kernel(const float *__res
 // ---- the subtraction ----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float combine1(float x, float y, bool has_y, float ca, float cb, float c0)
 {
-    if (!finite_f32(x) || (has_y && !finite_f32(y))) return __uint_as_float(0x7fc00000u);
+    if (!is_finite(x) || (has_y && !is_finite(y))) return __uint_as_float(0x7fc00000u);
     float v = ca * x;
     if (has_y) v = v + cb * y;
     return v + c0;

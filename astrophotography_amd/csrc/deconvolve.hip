@@ -20,6 +20,7 @@
 // trip count of the tap loop is what the register blocking is built on.  LDS per workgroup: (32 + 2 R)(60 + roundup4(8 + 2 R)) 4
 // bytes, 20.1 KiB at R = 12.
 #include "common.h"
+#include "np_exact.h"
 
 #include <cmath>
 
@@ -37,8 +38,6 @@ static_assert(kRuns * kTileH == kBlock, "a lane owns one run of the tile");
 struct Psf {
     float w[kMaxK * kMaxK];                                 // [K][K], row stride K = 2 R + 1 of the launch
 };
-
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 template <int R>
 struct Geo {
@@ -68,7 +67,7 @@ __device__ __forceinline__ void stage(float *tile, const float *__restrict__ src
         } else {
             const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
             v = in ? src[(size_t)gy * (size_t)W + (size_t)gx] : 0.0f;
-            if (RULE == kValidity) v = in && finite_f32(v) ? 1.0f : 0.0f;
+            if (RULE == kValidity) v = in && is_finite(v) ? 1.0f : 0.0f;
         }
         tile[lr * G::S + lc] = v;
     }
@@ -134,7 +133,7 @@ struct RatioArgs {
 __device__ __forceinline__ float ratio1(float d, float sum, const RatioArgs &a)
 {
     const float c = sum + a.sky;
-    if (!finite_f32(d)) return 0.0f;
+    if (!is_finite(d)) return 0.0f;
     if (!(c > 0.0f)) return 1.0f;
     float r;
     if (!a.damped) {
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void deconv_update_kernel(const float *__re
             float d[4];
             load4(data, base, xs, W, wide, d);
 #pragma unroll
-            for (int k = 0; k < 4; k++) o[k] = finite_f32(d[k]) ? o[k] + sky : __uint_as_float(0x7fc00000u);
+            for (int k = 0; k < 4; k++) o[k] = is_finite(d[k]) ? o[k] + sky : __uint_as_float(0x7fc00000u);
         }
         store4(out, base, xs, W, wide, o);
     }

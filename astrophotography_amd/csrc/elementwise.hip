@@ -11,6 +11,7 @@
 // Access pattern: 16 bytes per lane per load (float4 / 8 x u16), grid-stride over 2048 workgroups so
 // every CU holds several waves with independent 1 KiB wave-loads in flight.
 #include "common.h"
+#include "np_exact.h"
 
 namespace {
 using namespace apgpu;
@@ -145,14 +146,15 @@ __global__ __launch_bounds__(kBlock) void calibrate_kernel(const RawT *__restric
 
 // ------------------------------------------------------------------------------------------------
 // A1 flat normalisation.  np.nanmean(float32) = numpy's pairwise float32 sum taken over 8192-element
-// buffer pieces that are accumulated sequentially (verified against numpy 1.26.4 / 2.2.6, golden G7):
+// buffer pieces that are accumulated sequentially (the order np_exact.h states; verified against numpy 1.26.4 / 2.2.6,
+// golden G7):
 //   piece sum  : binary tree over 64 leaves of 128 elements; a leaf keeps 8 strided accumulators
 //                r[k] += a[8j+k] and reduces ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7))
 //   total      : ((0 + piece0) + piece1) + ...   in float32;  norm = f32(f64(total) / count)
 // Kernel 1: one wavefront per full piece, one lane per leaf, in-wave tree with the same pairing as
 //           numpy's recursion (halves of equal size).  NaNs count as 0 (np.nanmean) and are counted.
 // Kernel 2: one thread folds the piece sums in order, handles the ragged last piece with the
-//           general recursion, and writes norm.   Kernel 3: nflat = flat / norm.
+//           single-lane tree of np_exact.h, and writes norm.   Kernel 3: nflat = flat / norm.
 // ------------------------------------------------------------------------------------------------
 constexpr int kPiece = 8192;
 constexpr int kLeaf = 128;
@@ -167,61 +169,6 @@ __device__ __forceinline__ T nan0(T x, int &nans)
 }
 
 template <typename T>
-__device__ T leaf_sum(const T *a, int n, int &nans)
-{
-    // numpy pairwise_sum for 8 <= n <= 128
-    T r[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = nan0(a[k], nans);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) r[k] = r[k] + nan0(a[i + k], nans);
-    }
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res = res + nan0(a[i], nans);
-    return res;
-}
-
-struct PairwiseItem { int off, len; };
-
-// (one thread; its explicit stack lives in the caller's LDS: as local arrays with run-time indices it was 272 / 528 bytes of
-// scratch per thread of the kernel - round 5)
-template <typename T>
-__device__ T pairwise_generic(const T *a, int n, int &nans, PairwiseItem *stack, T *vals, int *state)
-{
-    // iterative form of numpy's recursion for the ragged last piece (n < 8192): explicit stack
-    typedef PairwiseItem Item;
-    int sp = 0, vp = 0;
-    stack[sp] = {0, n}; state[sp] = 0; sp++;
-    // post-order evaluation
-    while (sp > 0) {
-        Item it = stack[sp - 1];
-        int stt = state[sp - 1];
-        if (it.len < 8) {
-            T res = (T)0;
-            for (int i = 0; i < it.len; i++) res = res + nan0(a[it.off + i], nans);
-            vals[vp++] = res; sp--;
-        } else if (it.len <= kLeaf) {
-            vals[vp++] = leaf_sum(a + it.off, it.len, nans); sp--;
-        } else if (stt == 0) {
-            int n2 = it.len / 2; n2 -= n2 % 8;
-            state[sp - 1] = 1;
-            // evaluate left first, then right
-            stack[sp] = {it.off + n2, it.len - n2}; state[sp] = 0; sp++;
-            stack[sp] = {it.off, n2}; state[sp] = 0; sp++;
-        } else {
-            // both children evaluated: left was pushed last so it was evaluated first
-            T right = vals[--vp];
-            T left = vals[--vp];
-            vals[vp++] = left + right;
-            sp--;
-        }
-    }
-    return vals[0];
-}
-
-template <typename T>
 __global__ __launch_bounds__(kBlock) void flat_piece_sums_kernel(const T *__restrict__ flat, int64_t n,
                                                                 T *__restrict__ piece_sums,
                                                                 unsigned long long *__restrict__ nan_count)
@@ -233,7 +180,8 @@ __global__ __launch_bounds__(kBlock) void flat_piece_sums_kernel(const T *__rest
     for (int64_t piece = (int64_t)blockIdx.x * waves_per_block + wave; piece < npieces_full;
          piece += (int64_t)gridDim.x * waves_per_block) {
         int nans = 0;
-        T s = leaf_sum(flat + piece * kPiece + lane * kLeaf, kLeaf, nans);
+        const T *leaf = flat + piece * kPiece + lane * kLeaf;
+        T s = np_leaf_sum<T>(kLeaf, [&](int i) { return nan0(leaf[i], nans); });
         // numpy's recursion on 8192 = 64 leaves halves evenly: pair neighbours, then pairs of pairs ...
 #pragma unroll
         for (int d = 1; d < kWave; d <<= 1) {
@@ -285,12 +233,11 @@ __global__ __launch_bounds__(kBlock) void flat_norm_kernel(const T *__restrict__
     const int rem = (int)(n - npieces_full * kPiece);
     for (int t = threadIdx.x; t < rem; t += blockDim.x) stage[t] = flat[npieces_full * kPiece + t];
     __syncthreads();
-    __shared__ PairwiseItem pw_stack[32];
-    __shared__ T pw_vals[32];
-    __shared__ int pw_state[32];
+    // (one thread; its stack lives in LDS: as private arrays with run-time indices it would be scratch of every thread)
+    __shared__ NpSumStack<T> pw_stack;
     if (threadIdx.x != 0) return;
     int nans = 0;
-    if (rem > 0) res = res + pairwise_generic(stage, rem, nans, pw_stack, pw_vals, pw_state);
+    if (rem > 0) res = res + np_pairwise_sum<T>(rem, [&](int i) { return nan0(stage[i], nans); }, pw_stack);
     const unsigned long long bad = *nan_count + (unsigned long long)nans;
     const double cnt = (double)(n - (int64_t)bad);
     norm_out[0] = (T)((double)res / cnt);              // numpy 1.26: float32 / int -> float64 -> float32; float64 / int -> float64

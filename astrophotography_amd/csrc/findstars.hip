@@ -16,8 +16,9 @@
 //    combined across the wavefront and every lane evaluates the same scalar arithmetic; lane 0 writes the record.
 // 4. aperture_phot_kernel: one workgroup per source; exact circle-pixel overlap areas in float64, the annulus values
 //    compacted in row-major order into LDS, the clip on them (median by a workgroup-wide bitwise selection, numpy's
-//    pairwise float32 sums by one lane).
+//    float32 sums, np_exact.h, by one lane).
 #include "common.h"
+#include "np_exact.h"
 
 namespace {
 using namespace apgpu;
@@ -96,13 +97,6 @@ __global__ __launch_bounds__(256) void local_peaks_kernel(const float *__restric
 }
 
 // ---- 3. measurement ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-    return x;
-}
-
 // consts: 0 npixels - 1, 1 threshold_eff, 2 sharplo, 3 sharphi, 4 roundlo, 5 roundhi, 6 sigma^2, 7 p,
 //         8..12 x: sumg, sumgsq, sdgd, sdgds, sgdgd; 13..17 y: the same
 __global__ __launch_bounds__(256) void daofind_measure_kernel(const float *__restrict__ data, const float *__restrict__ conv, long long H,
@@ -163,12 +157,11 @@ __global__ __launch_bounds__(256) void daofind_measure_kernel(const float *__res
     const double xc = (double)j + dd[0], yc = (double)i + dd[1];
     r[0] = (double)j; r[1] = (double)i; r[2] = (double)ntap; r[3] = peak; r[4] = cpk; r[5] = sharp; r[6] = round1; r[7] = round2;
     r[8] = dd[0]; r[9] = dd[1]; r[10] = h[0]; r[11] = h[1]; r[12] = xc; r[13] = yc; r[14] = flux; r[15] = mag;
-    const double inf = __builtin_inf();
     bool ok = h[0] > 0.0 && h[1] > 0.0;
     ok = ok && sharp > consts[2] && sharp < consts[3] && round1 > consts[4] && round1 < consts[5] && round2 > consts[4] && round2 < consts[5];
     ok = ok && !(fabs(dd[0]) > (double)R) && !(fabs(dd[1]) > (double)R);
-    ok = ok && fabs(xc) < inf && fabs(yc) < inf && fabs(sharp) < inf && fabs(round1) < inf && fabs(round2) < inf && fabs(peak) < inf &&
-         fabs(flux) < inf;
+    ok = ok && is_finite(xc) && is_finite(yc) && is_finite(sharp) && is_finite(round1) && is_finite(round2) && is_finite(peak) &&
+         is_finite(flux);
     keep[k] = ok ? 1 : 0;
 }
 
@@ -220,88 +213,14 @@ __device__ double pixel_overlap(double x0, double x1, double y0, double y1, doub
     return a > 0.0 ? a : 0.0;
 }
 
-// the noaxis clip's float32 arithmetic, as sigclip_global.hip and autobadcol.hip define it (restated, one lane)
-template <int SQ>
-__device__ __forceinline__ float term(float x, float mean)
+// the noaxis clip's float32 sums in numpy's order (np_exact.h: n <= kAnnCap < 8192 is one piece), by one lane; st is in LDS
+template <typename F>
+__device__ float numpy_sum(int n, F f, NpSumStack<float> &st)
 {
-    if constexpr (SQ) { const float d = x - mean; return d * d; }
-    else return x;
+    return 0.0f + np_pairwise_sum<float>(n, f, st);
 }
 
-template <int SQ>
-__device__ float leaf_sum(const float *a, int n, float mean)
-{
-    if (n < 8) {
-        float res = 0.0f;
-        for (int i = 0; i < n; i++) res = res + term<SQ>(a[i], mean);
-        return res;
-    }
-    float r[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = term<SQ>(a[k], mean);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) r[k] = r[k] + term<SQ>(a[i + k], mean);
-    }
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res = res + term<SQ>(a[i], mean);
-    return res;
-}
-
-// numpy's pairwise sum of n <= kAnnCap (< 8192: one piece) values: halves rounded down to a multiple of 8, leaves <= 128
-template <int SQ>
-__device__ float numpy_sum(const float *a, int n, float mean)
-{
-    if (n <= 128) return 0.0f + leaf_sum<SQ>(a, n, mean);
-    int st_off[8], st_n[8], state[8];
-    float acc[8];
-    int sp = 0;
-    st_off[0] = 0; st_n[0] = n; state[0] = 0;
-    float val = 0.0f;
-    bool have = false;
-    while (true) {
-        if (!have) {
-            const int off = st_off[sp], cnt = st_n[sp];
-            if (cnt <= 128) {
-                val = leaf_sum<SQ>(a + off, cnt, mean);
-                have = true;
-            } else {
-                int n2 = cnt / 2;
-                n2 -= n2 % 8;
-                state[sp] = 0;
-                st_off[sp + 1] = off; st_n[sp + 1] = n2; state[sp + 1] = 0;
-                sp++;
-                continue;
-            }
-        }
-        if (sp == 0) break;
-        const int par = sp - 1;
-        if (state[par] == 0) {
-            acc[par] = val;
-            state[par] = 1;
-            int n2 = st_n[par] / 2;
-            n2 -= n2 % 8;
-            st_off[sp] = st_off[par] + n2; st_n[sp] = st_n[par] - n2; state[sp] = 0;
-            have = false;
-        } else {
-            val = acc[par] + val;
-            sp = par;
-        }
-    }
-    return 0.0f + val;
-}
-
-__device__ __forceinline__ unsigned f32_key(float x)
-{
-    const unsigned b = __float_as_uint(x);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float f32_from_key(unsigned k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
+using Key = OrderKey<float>;
 
 // k-th smallest key of buf[0 .. n) (0-based), all lanes of the workgroup take part; cnt is one LDS word
 __device__ unsigned block_select(const float *buf, int n, int k, int *cnt)
@@ -312,7 +231,7 @@ __device__ unsigned block_select(const float *buf, int n, int k, int *cnt)
         if (threadIdx.x == 0) *cnt = 0;
         __syncthreads();
         int less = 0;
-        for (int t = threadIdx.x; t < n; t += kPhotBlock) less += f32_key(buf[t]) < cand;
+        for (int t = threadIdx.x; t < n; t += kPhotBlock) less += Key::to(buf[t]) < cand;
         if (less) atomicAdd(cnt, less);
         __syncthreads();
         if (*cnt <= k) ans = cand;
@@ -324,9 +243,9 @@ __device__ unsigned block_select(const float *buf, int n, int k, int *cnt)
 // np.median of buf[0 .. n), n >= 1, no NaN
 __device__ float block_median(const float *buf, int n, int *cnt)
 {
-    const float hi = f32_from_key(block_select(buf, n, n / 2, cnt));
+    const float hi = Key::from(block_select(buf, n, n / 2, cnt));
     if (n & 1) return hi;
-    const float lo = f32_from_key(block_select(buf, n, n / 2 - 1, cnt));
+    const float lo = Key::from(block_select(buf, n, n / 2 - 1, cnt));
     return (lo + hi) / 2.0f;
 }
 
@@ -341,6 +260,7 @@ __global__ __launch_bounds__(kPhotBlock) void aperture_phot_kernel(const float *
     __shared__ int s_n, s_cnt, s_go;
     __shared__ int wave_cnt[kPhotBlock / kWave];
     __shared__ float s_lo, s_hi;
+    __shared__ NpSumStack<float> sum_stack;
     const int k = blockIdx.x;
     if (k >= n_src) return;
     const double cx = xc[k], cy = yc[k];
@@ -426,7 +346,7 @@ __global__ __launch_bounds__(kPhotBlock) void aperture_phot_kernel(const float *
         int m = 0;
         for (int t = 0; t < n_ann; t++) {
             const float x = buf[t];
-            if (fabsf(x) < __builtin_inff()) buf[m++] = x;
+            if (is_finite(x)) buf[m++] = x;
         }
         s_n = m;
     }
@@ -437,9 +357,9 @@ __global__ __launch_bounds__(kPhotBlock) void aperture_phot_kernel(const float *
         if (n <= 0) break;
         const float med = block_median(buf, n, &s_cnt);
         if (tid == 0) {
-            const float sm = numpy_sum<0>(buf, n, 0.0f);
+            const float sm = numpy_sum(n, [&](int i) { return buf[i]; }, sum_stack);
             const float mean = sm / (float)n;
-            const float s2 = numpy_sum<1>(buf, n, mean);
+            const float s2 = numpy_sum(n, [&](int i) { const float d = buf[i] - mean; return d * d; }, sum_stack);
             const float var = (float)((double)s2 / (double)n);
             const float sd = (float)sqrt((double)var);
             s_lo = (float)((double)med - (double)sd * sigma);

@@ -11,6 +11,7 @@
 // Parameter order inside this file: A, sigma_x, sigma_y, theta, B, x_mean, y_mean - a stage frees the first NF of them.
 // The model's "x" is the FIRST axis of the cut-out (np.mgrid), the row: a quirk of the reference that is kept.
 #include "common.h"
+#include "np_exact.h"
 
 #include <cmath>
 
@@ -19,58 +20,6 @@ namespace {
 
 constexpr int kFitMaxBox = APGPU_GAUSS2D_MAX_BOX;   // 2 * 76^2 floats = 46208 bytes of LDS
 constexpr int kRec = APGPU_GAUSS2D_REC;
-constexpr int kPwStack = 24;               // depth of numpy's pairwise recursion for <= 5776 values is 7
-
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-// numpy's pairwise float32 sum of a[0..n) (the add.reduce of np.mean over a contiguous float32 array), by one lane.
-__device__ float pw_leaf(const float *a, int n)
-{
-    if (n < 8) {
-        float res = 0.f;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    float r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    }
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
-__device__ float pairwise_sum_f32(const float *a, int n, int *stk, float *vstk)
-{
-    int sp = 0, vp = 0;                    // work items (offset, count, combine?) and finished sums, both in LDS
-    stk[0] = 0; stk[1] = n; stk[2] = 0; sp = 1;
-    while (sp > 0) {
-        --sp;
-        const int off = stk[3 * sp], cnt = stk[3 * sp + 1], combine = stk[3 * sp + 2];
-        if (combine) {
-            const float right = vstk[--vp], left = vstk[--vp];
-            vstk[vp++] = left + right;
-        } else if (cnt <= 128) {
-            vstk[vp++] = pw_leaf(a + off, cnt);
-        } else {
-            int n2 = cnt / 2;
-            n2 -= n2 % 8;
-            stk[3 * sp] = off; stk[3 * sp + 1] = cnt; stk[3 * sp + 2] = 1; ++sp;
-            stk[3 * sp] = off + n2; stk[3 * sp + 1] = cnt - n2; stk[3 * sp + 2] = 0; ++sp;      // the right half: done second
-            stk[3 * sp] = off; stk[3 * sp + 1] = n2; stk[3 * sp + 2] = 0; ++sp;                  // the left half: done first
-        }
-    }
-    return vstk[0];
-}
 
 struct Box {
     const float *d;      // the cut-out, row-major [Wb, Wb]
@@ -298,8 +247,7 @@ __global__ void __launch_bounds__(kWave) gauss2d_fit_kernel(const float *__restr
                                                             double *__restrict__ rec, int32_t *__restrict__ okflag)
 {
     extern __shared__ float lds[];
-    __shared__ int pw_stk[3 * kPwStack];
-    __shared__ float pw_val[kPwStack];
+    __shared__ NpSumStack<float> pw_stack;
     __shared__ float mean_sh;
     const int star = blockIdx.x, lane = threadIdx.x;
     if (star >= n) return;
@@ -338,7 +286,8 @@ __global__ void __launch_bounds__(kWave) gauss2d_fit_kernel(const float *__restr
         cnt += __popcll(m);
     }
     __syncthreads();
-    if (lane == 0) mean_sh = cnt > 0 ? pairwise_sum_f32(sd, cnt, pw_stk, pw_val) / (float)cnt : nanf("");
+    // np.mean of a contiguous float32 array: numpy's pairwise sum (np_exact.h; cnt <= 5776 is one piece), by one lane
+    if (lane == 0) mean_sh = cnt > 0 ? np_pairwise_sum<float>(cnt, [&](int i) { return sd[i]; }, pw_stack) / (float)cnt : nanf("");
     __syncthreads();
     const float mean32 = mean_sh;
     const float rms32 = (float)sqrt((double)mean32);

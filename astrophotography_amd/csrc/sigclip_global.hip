@@ -11,7 +11,7 @@
 // For float32 input numpy does all of this in float32 and the result depends on numpy's summation
 // tree, so the tree is reproduced exactly (bit-exact statistics -> bit-exact bad-pixel mask):
 //     np.sum      = sequential float32 fold of 8192-element pieces, each piece a pairwise tree over
-//                   128-element leaves with 8 strided accumulators  (numpy loops_utils.h.src)
+//                   128-element leaves with 8 strided accumulators  (np_exact.h states the order once)
 //     np.median   = exact order statistic (radix select on order-preserving keys, 11-bit digits: 3 levels for
 //                   float32, 6 for float64); even count -> float32(a + b) / 2
 //     np.var      = mean = sum / float32(n); float32 sum of (x - mean)^2; float32(float64(sum) / n)
@@ -26,6 +26,7 @@
 // sums), the tile count and the compaction (1 read + 1 write) - 5 reads + 1 write of the surviving values, 67 MB at
 // 4096^2 and resident in the 256 MB Infinity Cache after the first pass; 9 launches (round 1: 10 reads, 20 launches).
 #include "common.h"
+#include "np_exact.h"
 
 namespace {
 using namespace apgpu;
@@ -65,48 +66,16 @@ struct GState {
     unsigned long long wg_lo[kMaxPassGroups + 1], wg_hi[kMaxPassGroups + 1];   // per-workgroup extremes of a statistics pass
 };
 
-template <typename T> struct KeyOf;
-template <> struct KeyOf<float> {
-    using type = unsigned;
-    static constexpr int bits = 32;
-    __device__ static unsigned to(float x)
-    {
-        const unsigned b = __float_as_uint(x);
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    __device__ static float from(unsigned long long k64)
-    {
-        const unsigned k = (unsigned)k64;
-        const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        return __uint_as_float(b);
-    }
-};
-template <> struct KeyOf<double> {
-    using type = unsigned long long;
-    static constexpr int bits = 64;
-    __device__ static unsigned long long to(double x)
-    {
-        const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-    }
-    __device__ static double from(unsigned long long k)
-    {
-        const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-        return __longlong_as_double((long long)b);
-    }
-};
-template <typename T> constexpr int key_levels() { return (KeyOf<T>::bits + kDigit - 1) / kDigit; }
+template <typename T> constexpr int key_levels() { return (OrderKey<T>::bits + kDigit - 1) / kDigit; }
 // level l looks at key bits [shift, shift + width)
 template <typename T> __host__ __device__ constexpr int level_shift(int l)
 {
-    return KeyOf<T>::bits - kDigit * (l + 1) > 0 ? KeyOf<T>::bits - kDigit * (l + 1) : 0;
+    return OrderKey<T>::bits - kDigit * (l + 1) > 0 ? OrderKey<T>::bits - kDigit * (l + 1) : 0;
 }
 template <typename T> __host__ __device__ constexpr int level_width(int l)
 {
-    return l < key_levels<T>() - 1 ? kDigit : KeyOf<T>::bits - kDigit * (key_levels<T>() - 1);
+    return l < key_levels<T>() - 1 ? kDigit : OrderKey<T>::bits - kDigit * (key_levels<T>() - 1);
 }
-
-template <typename T> __device__ __forceinline__ bool is_finite(T x) { return fabs((double)x) < __builtin_inf(); }
 
 // ---- order-preserving compaction: tile counts -> scan -> scatter -------------------------------
 // mode 0: keep finite values of `data` (length n, host-known); mode 1: keep lo <= x <= hi of the
@@ -114,7 +83,7 @@ template <typename T> __device__ __forceinline__ bool is_finite(T x) { return fa
 template <int MODE, typename T>
 __device__ __forceinline__ bool keep_pred(T x, T lof, T hif)
 {
-    if constexpr (MODE == 0) return is_finite<T>(x);
+    if constexpr (MODE == 0) return is_finite(x);
     else return (x >= lof) && (x <= hif);
 }
 
@@ -329,27 +298,6 @@ __device__ __forceinline__ T var_mean(const GState *st, long long m)
 __device__ __forceinline__ int ridx(int i) { return i + (i >> 6); }
 constexpr int kRaggedLds = kPiece + kPiece / 64;
 
-template <int SQ, typename T>
-__device__ T ragged_leaf(const T *rag, int off, int n, T mean)
-{
-    if (n < 8) {
-        T res = 0;
-        for (int i = 0; i < n; i++) res = res + tr<SQ, T>(rag[ridx(off + i)], mean);
-        return res;
-    }
-    T r[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = tr<SQ, T>(rag[ridx(off + k)], mean);
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) r[k] = r[k] + tr<SQ, T>(rag[ridx(off + i + k)], mean);
-    }
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res = res + tr<SQ, T>(rag[ridx(off + i)], mean);
-    return res;
-}
-
 // numpy's recursion over the ragged piece (rem < 8192 values staged in LDS), in parallel: every 64th element descends the
 // split tree to its leaf (leaves are 64 .. 128 elements long, so each leaf is found by the thread at the first multiple of
 // 64 inside it), the leaves are summed side by side, and the tree is folded level by level, deepest first; a node's value
@@ -369,20 +317,18 @@ __device__ T ragged_tree_sum(const T *ragged, int rem, T mean, T *vals /* LDS [k
         path_off[d] = off;
         path_n[d] = internal ? n : 0;
         if (internal) {
-            int n2 = n / 2;
-            n2 -= n2 % 8;
+            const int n2 = np_left_half(n);
             if (p < off + n2) n = n2;
             else { off += n2; n -= n2; }
         }
     }
     const bool owner = valid && (off + 63) / 64 == t;
-    if (owner) vals[t] = ragged_leaf<SQ, T>(ragged, off, n, mean);
+    if (owner) vals[t] = np_leaf_sum<T>(n, [&](int i) { return tr<SQ, T>(ragged[ridx(off + i)], mean); });
     __syncthreads();
 #pragma unroll
     for (int d = 7; d >= 0; d--) {
         if (owner && path_n[d] > 0 && path_off[d] == off) {
-            int n2 = path_n[d] / 2;
-            n2 -= n2 % 8;
+            const int n2 = np_left_half(path_n[d]);
             vals[t] = vals[t] + vals[(path_off[d] + n2 + 63) / 64];
         }
         __syncthreads();
@@ -435,16 +381,17 @@ __device__ void wave_pick_digit(const unsigned *h, long long k, int lane, DigitP
 template <typename T>
 __device__ double median_of_pick(long long m, unsigned long long prefix, int width, const DigitPick &pk, unsigned long long below)
 {
-    using K = KeyOf<T>;
+    using K = OrderKey<T>;
+    using KT = typename K::U;                               // the state holds every key in 64 bits: narrowed for from()
     if (m <= 0) return __builtin_nan("");
-    const T vhi = K::from((prefix << width) | (unsigned long long)pk.digit);
+    const T vhi = K::from((KT)((prefix << width) | (unsigned long long)pk.digit));
     if (m & 1) return (double)vhi;
     // rank m/2 - 1: the same key again if the searched rank is not the first of its bin; otherwise the highest occupied
     // lower bin of this prefix, otherwise the largest key below the prefix
     T vlo;
     if (pk.newk >= 1) vlo = vhi;
-    else if (pk.dlow >= 0) vlo = K::from((prefix << width) | (unsigned long long)pk.dlow);
-    else vlo = K::from(below);
+    else if (pk.dlow >= 0) vlo = K::from((KT)((prefix << width) | (unsigned long long)pk.dlow));
+    else vlo = K::from((KT)below);
     const T t = vlo + vhi;                                  // np.mean of the two middle values, in T
     return (double)(T)((double)t / 2.0);
 }
@@ -465,8 +412,8 @@ template <typename T, int SUM, int KIND>
 __global__ __launch_bounds__(kScanBlock) void pass_kernel(const T *__restrict__ b0, const T *__restrict__ b1,
                                                          GState *__restrict__ st, T *__restrict__ piece_sums, int slot, int level)
 {
-    using K = KeyOf<T>;
-    using KT = typename K::type;
+    using K = OrderKey<T>;
+    using KT = typename K::U;
     const IterState s = st->it[slot];
     if (s.done) return;
     const T *src = s.cur ? b1 : b0;
@@ -832,7 +779,7 @@ __global__ __launch_bounds__(kBlock) void close_count_kernel(const T *__restrict
 template <typename T>
 __global__ void publish_kernel(const GState *st, int slot, double *out)
 {
-    using K = KeyOf<T>;
+    using K = OrderKey<T>;
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const IterState s = st->it[slot];
     const long long m = s.m;
@@ -844,8 +791,8 @@ __global__ void publish_kernel(const GState *st, int slot, double *out)
     out[4] = st->hi;
     out[5] = (double)s.iter;
     out[6] = (double)m;
-    out[7] = m > 0 ? (double)K::from(st->min_key) : nan;
-    out[8] = m > 0 ? (double)K::from(st->max_key) : nan;
+    out[7] = m > 0 ? (double)K::from((typename K::U)st->min_key) : nan;
+    out[8] = m > 0 ? (double)K::from((typename K::U)st->max_key) : nan;
     out[9] = 0.0;
 }
 

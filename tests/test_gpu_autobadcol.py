@@ -171,6 +171,23 @@ def test_long_lines_exact(shape, dtype):
         assert_biteq(std[i:i + 1], np.array([np.nanstd(x)], np.float64), 'std at %d' % i)
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('L,window_len', [(400, 7), (400, 9), (400, 129), (400, 137), (400, 257), (1100, 2001)])
+def test_window_sums_on_both_sides_of_numpys_boundaries(L, window_len, dtype):
+    """sigma = 1e300 clips nothing, so every window's count is its length and mean and std are numpy's sums of exactly that
+    many values: with the one-sided windows at the ends of the line the lengths run over 4 .. 9 (the leaf's short form),
+    65 .. 137 (leaf against tree at 128), 129 .. 257 and 1001 .. 1100."""
+    import torch
+    from astrophotography_amd import ops
+    rng = np.random.default_rng(L + window_len)
+    v = (1000.0 + 50.0 * rng.standard_normal(L)).astype(dtype)
+    r = ops.sliding_clipped_stats(torch.from_numpy(v).cuda(), window_len, sigma=1e300)
+    hw = (window_len - 1) // 2
+    wins = [v[max(0, i - hw):i + hw + 1] for i in range(L)]
+    assert_biteq(r['mean'].cpu().numpy(), np.array([np.nanmean(x) for x in wins], np.float64), 'mean, window %d' % window_len)
+    assert_biteq(r['std'].cpu().numpy(), np.array([np.nanstd(x) for x in wins], np.float64), 'std, window %d' % window_len)
+
+
 def test_u16_and_integer_inputs():
     import torch
     from astrophotography_amd import ops

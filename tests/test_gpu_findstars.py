@@ -336,6 +336,27 @@ def test_aperture_photometry_matches_the_model(fwhm):
     assert np.array_equal(got['aperture_sum'][fin], exp[fin])
 
 
+@pytest.mark.parametrize('radii,lo,hi', [((2.0, 1.0, 1.7), 3, 8), ((2.0, 5.0, 8.1), 120, 129), ((2.0, 5.0, 8.3), 129, 138),
+                                         ((2.0, 5.0, 10.3), 250, 258)])
+def test_annulus_counts_on_both_sides_of_numpys_boundaries(radii, lo, hi):
+    """Thin annuli on a 64 x 64 field with stars in it (the clip removes them): the clip's float32 sums run over a handful of
+    values (numpy's short form below 8), over counts on both sides of 128 (one leaf against the split tree) and over about
+    250; the annuli of the sources at the edges are cut off by the image.  bkg_median depends on the sums only through the
+    clip's bounds, so a last-bit error would seldom show here: the exact check of the sum is the host test of np_exact.h."""
+    from astrophotography_amd import ops
+    img = field(64, 64, seed=64, nstars=6, noise=3.0)
+    xc = [32.0, 31.5, 30.25, 20.7, 40.37, 33.113, 0.0, 63.0, 2.3, 25.5]
+    yc = [32.0, 30.5, 33.4, 41.1, 22.81, 28.004, 30.0, 63.0, 60.1, 36.0]
+    vals = [fm.annulus_values(img, x, y, radii[1], radii[2]) for x, y in zip(xc, yc)]
+    got = ops.aperture_photometry(dev(img), xc, yc, radii=radii)
+    counts = got['n_annulus'].cpu().numpy()
+    assert np.array_equal(counts, [v.size for v in vals]) and counts.min() > 0
+    assert counts.min() <= lo and counts.max() >= hi and np.any((counts > lo) & (counts < hi)), counts
+    if lo < 128 <= hi:
+        assert np.any(counts == 128) and np.any(counts < 128) and np.any(counts > 128), counts
+    assert_biteq(got['bkg_median'].cpu().numpy(), np.array([fm.annulus_clip(v)[1] for v in vals], np.float32), 'bkg_median')
+
+
 def test_annulus_clip_equals_astropy_g16():
     """Every G16 vector laid, in row-major order, into the annulus of one source (radii 17 .. 26, 1252 pixels), the rest of the
     annulus NaN (dropped before the clip): the kernel's bkg_median equals astropy's median, compared as float32, exactly."""

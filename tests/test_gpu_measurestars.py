@@ -146,6 +146,49 @@ def test_box_sizes_corner_cap_and_empty_box():
     assert not r['fit_ok'].any() and np.all(r['ampl_err'] == 0) and np.all(r['circular'])
 
 
+@pytest.mark.parametrize('negatives', [23, 16, 6])
+def test_weights_mean_on_both_sides_of_one_numpy_leaf(negatives):
+    """The kernel's only numpy sum is the float32 mean of the positive pixels, which becomes the standard deviation of the
+    others.  In the smallest box the op takes (12 pixels: 144 values; odd widths are an error) 23, 16 or 6 border pixels are
+    negative, so the mean runs over 121 values (one leaf, with a tail of 1), over 128 (the largest leaf) and over 138 (a
+    split tree: 64 + 74).  The fit does not publish the mean; the reduced chi^2 does depend on it: the terms of the negative
+    pixels are divided by it, and they are a fifth of the sum or more.  The chi^2 of the device's own answer is recomputed on
+    the host with the model's weights (numpy's mean).
+    Bound: both sides add the same 144 float64 terms; they differ in the order of the adds (<= 144 eps relative), in exp
+    (1 ulp each, argument <= 50 with a few roundings: <= 5e-14 relative in A E <= 4000, i.e. <= 2e-10 in the model) and each
+    term moves by 2 |d - m| / sd^2 times that, |d - m| / sd^2 < 1: <= 144 * 4e-10 absolute on a chi^2 of several hundred,
+    under 1e-9 relative.  One float32 ulp in the standard deviation of the negative pixels (two ulps of the mean) moves the
+    chi^2 by over ten times as much, which the test checks on the host.  The limit of this test: one ulp of the mean is half
+    an ulp of that standard deviation and may round away, so only an error of two ulps or more in the sum is sure to show;
+    the exact check of the sum itself is tests/test_host_cpu.py::test_np_exact_header_equals_numpy."""
+    from astrophotography_amd import ops
+    Wb = 12
+    img = synthetic(40, 40, 20.3, 19.6, 3.0)
+    y0 = x0 = 20 - Wb // 2                                      # the box of a star at (19.6, 20.3): [rint(c) - Wb / 2, ...)
+    border = [(0, c) for c in range(Wb)] + [(Wb - 1, c) for c in range(Wb)]
+    for dy, dx in border[:negatives]:
+        img[y0 + dy, x0 + dx] = -20.0
+    got = ops.gauss2d_fit(torch.from_numpy(img).cuda(), [19.6], [20.3], [4000.0], [50.0], 3.0, box_width=Wb)
+    assert got['fit_ok'][0] and (int(got['xmin'][0]), int(got['ymin'][0])) == (x0, y0)
+    cut = img[y0:y0 + Wb, x0:x0 + Wb]
+    var = np.where(cut > 0, cut, np.float32(1))
+    count = int((var != 1).sum())
+    assert count == Wb * Wb - negatives
+    p, _ = mm.params(got, 0, got['xmin'][0], got['ymin'][0])
+    model, _ = mm.model_and_jacobian(p, Wb)
+
+    def rchisq(sd):
+        return float(np.sum(((cut.astype(np.float64) - model) / sd.astype(np.float64)) ** 2)) / (Wb * Wb - 7)
+    sd = mm.weights_of(cut)[1]
+    off = np.where(var != 1, sd, np.nextafter(sd, np.float32(np.inf)))             # the negative pixels', one ulp up
+    want, moved = rchisq(sd), rchisq(off)
+    tol = 1e-9
+    print('%d values: rchisq %.17g, host %.17g, relative difference %.2e; one ulp in the others moves it by %.2e' % (
+        count, got['rchisq'][0], want, abs(got['rchisq'][0] - want) / want, abs(moved - want) / want))
+    assert abs(moved - want) / want > 10 * tol
+    assert abs(got['rchisq'][0] - want) / want <= tol
+
+
 def test_measure_fwhm_and_script_end_to_end(tmp_path):
     yaml = pytest.importorskip('yaml')
     import astrophotography_amd as ap

@@ -64,6 +64,20 @@ def test_flat_normalize_large(ops, apref):
         assert_biteq(host(nflat), rn, f'n={n}')
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('n', [7, 8, 9, 128, 129, 136, 255, 256, 257, 1001])
+def test_flat_normalize_short_flats(ops, apref, n, dtype):
+    """Flats of less than one 8192-element piece, one NaN in each: the whole sum is the single-lane tree of csrc/np_exact.h, on
+    both sides of the leaf's short form (8), of leaf against tree (128) and of the first uneven split."""
+    rng = np.random.default_rng(n)
+    a = rng.normal(30000, 300, n).astype(dtype)
+    a[n // 3] = np.nan
+    nflat, norm = ops.flat_normalize(dev(a, ops))
+    rn, rnorm = apref.flat_normalize(a)
+    assert_biteq(host(norm)[0:1], np.array([rnorm], dtype), f'n={n}')
+    assert_biteq(host(nflat), rn, f'n={n}')
+
+
 # ---- A2 (+A5) golden ------------------------------------------------------------------------------------
 def test_calibrate_golden(ops):
     g = load_golden('g1_calibrate.npz')

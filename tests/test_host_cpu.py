@@ -465,6 +465,84 @@ def test_sort_networks_pass_the_zero_one_principle(tmp_path):
     assert 'NP  64 T 4:  750 instructions' in r.stdout          # the headline kernel's network (890 with sort4 + Batcher)
 
 
+def test_np_exact_header_equals_numpy(tmp_path):
+    """csrc/np_exact.h is the one statement of numpy's summation order and of the order-preserving float key that the
+    bit-exact statistics kernels share.  tools/np_exact_check.cpp runs it on the host; NumPy itself is the reference,
+    everything bit for bit: np.add.reduce (leaf, tree and 8192-element pieces, on both sides of every boundary), the sum of
+    squared deviations, the NaN-as-zero sum with its NaN count, and the key (strictly monotone, inverted exactly)."""
+    import struct
+    import subprocess
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        pytest.skip('no hipcc')
+    exe = str(tmp_path / 'np_exact_check')
+    r = subprocess.run([hipcc, '--cuda-host-only', '-O2', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(ROOT, 'astrophotography_amd', 'csrc'),
+                        os.path.join(ROOT, 'tools', 'np_exact_check.cpp'), '-o', exe],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:]
+
+    rng = np.random.default_rng(20261018)
+    lengths = list(range(301)) + [511, 512, 513, 1000, 1023, 1024, 1025, 4095, 4096, 4097, 5776, 8191, 8192, 8193, 8192 + 129, 20000]
+    records = []                                                            # (kind, array, m)
+    for dt in (np.float32, np.float64):
+        for n in lengths:
+            records.append(('S', (rng.standard_normal(n) * 1e3).astype(dt), None))
+        mixed = rng.choice([-1.0, 1.0], 20000) * np.exp2(rng.uniform(-30, 30, 20000))
+        records.append(('S', mixed.astype(dt), None))
+        for n in (7, 8, 129, 4097):
+            a = (rng.standard_normal(n) * 1e3).astype(dt)
+            a[rng.choice(n, max(1, n // 50), replace=False)] = np.nan
+            records.append(('S', a, None))
+        fi, bits = np.finfo(dt), np.dtype(dt).itemsize * 8
+        ut = np.uint32 if dt is np.float32 else np.uint64
+        special = np.array([0.0, fi.smallest_subnormal, fi.smallest_normal - fi.smallest_subnormal, fi.smallest_normal, 1.0, fi.max,
+                            np.inf], dtype=dt)
+        pats = rng.integers(0, 2 ** bits, 10000, dtype=ut, endpoint=False).view(dt)
+        records.append(('K', np.concatenate([special, -special, pats[~np.isnan(pats)]]).astype(dt), None))
+    path = str(tmp_path / 'records.bin')
+    with open(path, 'wb') as fh:
+        for i, (kind, a, _) in enumerate(records):
+            with np.errstate(all='ignore'):
+                m = a.dtype.type(a.mean()) if a.size and kind == 'S' else a.dtype.type(0)
+            records[i] = (kind, a, m)
+            fh.write(struct.pack('<iiqd', ord(kind), a.itemsize, a.size, float(m) if np.isfinite(m) else 0.0))
+            fh.write(np.ascontiguousarray(a).tobytes())
+    r = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(records)
+
+    n_sums = n_nan = 0
+    for (kind, a, m), line in zip(records, lines):
+        dt, ut = a.dtype.type, (np.uint32 if a.itemsize == 4 else np.uint64)
+        f = line.split()
+        assert f[0] == kind
+        bits_of = lambda v: int(np.asarray(v, dtype=dt).view(ut))
+        if kind == 'S':
+            got_sum, got_sq, got_nansum, got_nans = int(f[1], 16), int(f[2], 16), int(f[3], 16), int(f[4])
+            if np.isnan(a).any():
+                assert got_nansum == bits_of(np.nansum(a)) and got_nans == int(np.isnan(a).sum()), a.size
+                n_nan += 1
+            else:
+                d = a - m
+                assert got_sum == bits_of(np.add.reduce(a)), (a.dtype, a.size)
+                assert got_sq == bits_of(np.add.reduce(d * d)), (a.dtype, a.size)
+                assert got_nansum == got_sum and got_nans == 0
+                n_sums += 1
+        else:
+            keys = np.array([int(x, 16) for x in f[1::2]], dtype=np.uint64)
+            back = np.array([int(x, 16) for x in f[2::2]], dtype=np.uint64)
+            assert np.array_equal(back, a.view(ut).astype(np.uint64))                   # from(to(x)) == x, bitwise
+            assert a[0] == 0 and a[7] == 0 and np.signbit(a[7]) and keys[7] < keys[0]   # to(-0) < to(+0)
+            _, first = np.unique(a.view(ut), return_index=True)
+            order = first[np.argsort(keys[first], kind='stable')]
+            v, k = a[order], keys[order]
+            assert np.all(k[1:] > k[:-1])
+            zeros = (v[:-1] == 0) & (v[1:] == 0) & np.signbit(v[:-1]) & ~np.signbit(v[1:])
+            assert np.all((v[1:] > v[:-1]) | zeros)                                     # sorted by key = sorted by value
+    assert n_sums == 2 * (len(lengths) + 1) and n_nan == 8
+
+
 def test_mad_window_crossing_equals_scan():
     """stack_reduce.h:mad_std_window (round 4) finds the minimum over the windows [L, L + k1] of max(|x_L - med|, |x_(L+k1) - med|)
     by a binary search for the crossing of the two end deviations instead of scanning every window.  The same two procedures in

@@ -54,6 +54,10 @@ report('  axis_nanmedian axis 0 (columns), 1 x 4096^2 f32', t(lambda: ops.axis_n
 report('  axis_nanmedian axis 1 (rows), 1 x 4096^2 f32', t(lambda: ops.axis_nanmedian(frame, 1), a.reps), frame.numel() * 4)
 med = ops.axis_nanmedian(frame, 0)
 report('  sliding_clipped_stats, 4096 f32, window 11', t(lambda: ops.sliding_clipped_stats(med, 11), a.reps), med.numel() * 4)
+med64 = med.double()
+report('  sliding_clipped_stats, 4096 f64, window 11', t(lambda: ops.sliding_clipped_stats(med64, 11), a.reps), med.numel() * 8)
+report('  sliding_clipped_stats, 4096 f32, window 301', t(lambda: ops.sliding_clipped_stats(med, 301), a.reps), med.numel() * 4)
+report('  sliding_clipped_stats, 4096 f64, window 301', t(lambda: ops.sliding_clipped_stats(med64, 301), a.reps), med.numel() * 8)
 del frame
 
 N = 8 if a.quick else 64
