@@ -28,6 +28,7 @@ _LAZY = {
     'ApDebayer': ('.core.ApDebayer', 'ApDebayer'),
     'ApContinuumSubtract': ('.core.ApContinuumSubtract', 'ApContinuumSubtract'),
     'ApDeconvolve': ('.core.ApDeconvolve', 'ApDeconvolve'),
+    'ApMultiscale': ('.core.ApMultiscale', 'ApMultiscale'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -24,6 +24,11 @@ REGISTER_MAX_K, REGISTER_MAX_STARS = 64, 4096           # APGPU_REGISTER_MAX_K, 
 COMPOSITE_MAX_VARIANTS, TONE_TABLE_LEN = 16, 10241      # APGPU_COMPOSITE_MAX_VARIANTS, APGPU_TONE_TABLE_LEN
 BLUR_MAX_RADIUS, BLUR_TILE_H, BLUR_TILE_W = 32, 32, 64  # APGPU_BLUR_MAX_RADIUS, APGPU_BLUR_TILE_H, APGPU_BLUR_TILE_W
 DECONV_MAX_RADIUS, DECONV_TILE_H, DECONV_TILE_W = 12, 32, 64    # APGPU_DECONV_MAX_RADIUS, APGPU_DECONV_TILE_H, APGPU_DECONV_TILE_W
+STARLET_MAX_SCALES, STARLET_TILE_H, STARLET_TILE_W, STARLET_CHAIN = 6, 32, 64, 8     # APGPU_STARLET_MAX_SCALES, _TILE_H, _TILE_W, _CHAIN
+STARLET_TILE_MAX_SPACING, STARLET_TILE_MAX_AUTO = 8, 0  # APGPU_STARLET_TILE_MAX_SPACING, APGPU_STARLET_TILE_MAX_AUTO
+STARLET_MODE = {'hard': 0, 'soft': 1}                   # APGPU_STARLET_HARD, APGPU_STARLET_SOFT
+STARLET_FIRST, STARLET_LAST = 1, 2                      # APGPU_STARLET_FIRST, APGPU_STARLET_LAST
+STARLET_FORM = {'auto': 0, 'tile': 1, 'direct': 2}      # APGPU_STARLET_FORM_*
 
 
 class ApGpuError(RuntimeError):
@@ -158,6 +163,13 @@ SIGNATURES = {
     'apgpu_richardson_lucy_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_float, C.c_float,
                                             C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.c_void_p]),
+    'apgpu_starlet_step_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                         C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    'apgpu_starlet_plane1_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    'apgpu_starlet_ws_bytes': (C.c_size_t, [C.c_int64, C.c_int64]),
+    'apgpu_starlet_planes_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'apgpu_multiscale_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
+                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -2290,3 +2290,159 @@ def richardson_lucy(data, psf, sky, niter=30, damp=0.0, gain=1.0, readnoise=0.0,
     report = dict(start=level, niter=niter, radius=R, damp=float(damp), sky=float(np.float32(sky)), gain=float(gain), readnoise=float(readnoise),
                   min_weight=float(min_weight), launches=1 + 2 * niter)
     return out, report
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F13: ApMultiscale - starlet (B3-spline a trous) denoise and sharpen (csrc/multiscale.hip; the reference has no such
+# stage: the arithmetic is this project's definition, include/apgpu.h F13, tests/multiscale_model.py)
+STARLET_MAX_SCALES = _lib.STARLET_MAX_SCALES
+STARLET_TAPS = np.array([1.0, 4.0, 6.0, 4.0, 1.0], np.float64) / 16.0
+
+
+def starlet_noise_constants(J):
+    """float64 [J]: the standard deviation of the planes w_1 .. w_J for unit white noise far from borders and holes, computed from
+    the taps as the 2-norm of each plane's impulse response."""
+    import math
+    J = _starlet_scales(J)
+    kern, out = np.ones(1), []
+    for j in range(J):
+        up = np.zeros(4 * (1 << j) + 1)
+        up[::1 << j] = STARLET_TAPS
+        nxt = np.convolve(kern, up)                                          # the impulse response of c_{j+1} along one axis
+        prev = np.pad(kern, (nxt.size - kern.size) // 2)
+        plane = np.outer(prev, prev) - np.outer(nxt, nxt)
+        out.append(math.sqrt(float((plane * plane).sum())))
+        kern = nxt
+    return np.array(out)
+
+
+def _starlet_scales(J):
+    if int(J) != J or not 1 <= int(J) <= STARLET_MAX_SCALES:
+        raise ValueError('the number of scales must be 1 .. %d, got %r' % (STARLET_MAX_SCALES, J))
+    return int(J)
+
+
+def _starlet_per_scale(v, J, name):
+    v = np.asarray(v, np.float64).reshape(-1)
+    if v.size == 1:
+        v = np.repeat(v, J)
+    if v.size != J:
+        raise ValueError('%s needs one value or %d (one per scale), got %d' % (name, J, v.size))
+    return v
+
+
+def _starlet_mode(mode):
+    if mode not in _lib.STARLET_MODE:
+        raise ValueError('Unexpected mode %r. Allowed values are: %s' % (mode, sorted(_lib.STARLET_MODE)))
+    return _lib.STARLET_MODE[mode]
+
+
+def starlet_workspace(shape, device):
+    """A workspace for starlet_planes and multiscale on images of this shape (8 bytes per pixel: the two ping-pong planes)."""
+    return torch.empty(_lib.load().apgpu_starlet_ws_bytes(int(shape[0]), int(shape[1])), dtype=torch.uint8, device=device)
+
+
+def _starlet_ws(ws, data):
+    need = _lib.load().apgpu_starlet_ws_bytes(data.shape[0], data.shape[1])
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=data.device)
+    _need_cuda(ws)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
+        raise ValueError('ws must be a contiguous, 16-byte aligned uint8 device tensor of at least %d bytes (ops.starlet_workspace)' % need)
+    return ws
+
+
+def starlet_step(c, spacing, out=None, plane=None, acc=None, threshold=0.0, gain=1.0, g_res=1.0, mode='hard', first=True, last=False,
+                 form='auto'):
+    """One launch of F13: c_j -> c_{j+1} at `spacing` = 2^j (1 .. 32) by normalised convolution with the B3 taps, NaN / inf pixels
+    being holes that stay NaN.  out: the tensor for c_{j+1} (None: a new one; False: not wanted).  plane: a tensor that receives
+    w_{j+1} = c_j - c_{j+1}.  acc: the accumulator of the reconstruction: written as +0 + gain T(w) when `first`, else added to;
+    `last` adds g_res c_{j+1} on top.  form: 'auto', 'tile' (spacing <= 8) or 'direct': the same bits either way.
+    Returns c_{j+1} (None with out=False)."""
+    c = _image_f32(c, 'c')
+    if form not in _lib.STARLET_FORM:
+        raise ValueError('Unexpected form %r. Allowed values are: %s' % (form, sorted(_lib.STARLET_FORM)))
+    if out is None:
+        out = torch.empty_like(c)
+    elif out is False:
+        out = None
+    for t in (out, plane, acc):
+        if t is not None:
+            _need_cuda(t)
+            if t.dtype != torch.float32 or tuple(t.shape) != tuple(c.shape) or not t.is_contiguous():
+                raise ValueError('out, plane and acc must be contiguous float32 device tensors of the image shape')
+    flags = (_lib.STARLET_FIRST if first else 0) | (_lib.STARLET_LAST if last else 0)
+    check(_lib.load().apgpu_starlet_step_f32(_ptr(c), c.shape[0], c.shape[1], int(spacing), _ptr(out), _ptr(plane), _ptr(acc),
+                                             float(threshold), float(gain), float(g_res), _starlet_mode(mode), flags, _lib.STARLET_FORM[form],
+                                             _stream()))
+    return out
+
+
+def starlet_plane1(image, out=None):
+    """w_1 = c_0 - c_1 alone (one launch): the plane the image noise is measured in."""
+    image = _image_f32(image, 'image')
+    out = _deconv_out(out, image, image)
+    check(_lib.load().apgpu_starlet_plane1_f32(_ptr(image), image.shape[0], image.shape[1], _ptr(out), _stream()))
+    return out
+
+
+def starlet_planes(image, J=4, ws=None, out=None):
+    """The transform itself: a float32 tensor [J + 1, H, W] holding w_1 .. w_J and the smooth residual c_J; their float32 sum in
+    this order is the image to within rounding.  Holes (NaN / inf pixels) are NaN in every plane.  J launches."""
+    image = _image_f32(image, 'image')
+    J = _starlet_scales(J)
+    shape = (J + 1,) + tuple(image.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=image.device)
+    else:
+        _need_cuda(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError('out must be a contiguous float32 device tensor of shape %s' % (shape,))
+    ws = _starlet_ws(ws, image)
+    check(_lib.load().apgpu_starlet_planes_f32(_ptr(image), image.shape[0], image.shape[1], J, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out
+
+
+def starlet_sigma(image):
+    """The image noise: the clipped standard deviation (sigma 3, 5 iterations) of plane 1 over the noise constant of plane 1.
+    NaN when plane 1 has no finite pixel."""
+    std = float(sigclip_global(starlet_plane1(image), 3.0, maxiters=5).cpu().numpy()[2])
+    return std / float(starlet_noise_constants(1)[0])
+
+
+def multiscale(image, J=4, k=(3.0, 3.0, 2.0, 1.0), gains=1.0, g_res=1.0, mode='hard', sigma=None, ws=None, out=None):
+    """Noise reduction and sharpening by scale of a float32 image [H, W] whose NaN / inf pixels are holes (include/apgpu.h F13;
+    tests/multiscale_model.py): plane j of the starlet transform is cut at t_j = float32(k_j sigma sigma_e[j-1]) ('hard': smaller
+    coefficients become 0; 'soft': all shrink by t_j; k_j = 0: untouched), weighted by gains[j-1] and summed with g_res times the
+    smooth residual.  k, gains: one value per scale, or one for all.  sigma: the image noise; None measures it (starlet_sigma) and
+    raises RuntimeError when that gives no finite value.  ws: a uint8 device workspace (starlet_workspace) or None; out: the output
+    tensor or None.  J launches on the current stream, nothing else inside the loop.
+
+    Returns (image, report): report has sigma, t (float32 [J]), J, mode, k, gains, g_res."""
+    import math
+    image = _image_f32(image, 'image')
+    J = _starlet_scales(J)
+    k, gains = _starlet_per_scale(k, J, 'k'), _starlet_per_scale(gains, J, 'gains')
+    if not np.all(k >= 0.0) or not np.all(np.isfinite(k)):
+        raise ValueError('the thresholds k must be finite and >= 0, got %s' % (k.tolist(),))
+    g = gains.astype(np.float32)
+    gr = np.float32(g_res)
+    if not np.all(np.isfinite(g)) or not np.isfinite(gr):
+        raise ValueError('the gains must be finite, got %s and %r' % (gains.tolist(), g_res))
+    m = _starlet_mode(mode)
+    if sigma is None:
+        sigma = starlet_sigma(image)
+        if not math.isfinite(sigma):
+            raise RuntimeError('Could not measure the noise of the image (plane 1 has no finite standard deviation): pass sigma.')
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and math.isfinite(sigma)):
+        raise ValueError('sigma must be finite and >= 0, got %r' % sigma)
+    se = starlet_noise_constants(J)
+    t = np.array([np.float32(float(k[j]) * sigma * float(se[j])) for j in range(J)], np.float32)
+    if not np.all(np.isfinite(t)):
+        raise ValueError('the thresholds overflow float32: %s' % (t.tolist(),))
+    out = _deconv_out(out, image, image)
+    ws = _starlet_ws(ws, image)
+    check(_lib.load().apgpu_multiscale_f32(_ptr(image), image.shape[0], image.shape[1], J, t.ctypes.data_as(C.POINTER(C.c_float)),
+                                           g.ctypes.data_as(C.POINTER(C.c_float)), float(gr), m, _ptr(out), _ptr(ws), ws.numel(), _stream()))
+    return out, dict(sigma=sigma, t=t, J=J, mode=mode, k=k, gains=g.astype(np.float64), g_res=float(gr))

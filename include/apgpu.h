@@ -777,6 +777,62 @@ int apgpu_richardson_lucy_f32(const float *data, int64_t height, int64_t width, 
                               float readnoise, float damp, int32_t niter, float start_level, const float *start_plane, float min_weight,
                               float *out, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F13 ApMultiscale: noise reduction and detail enhancement by scale with the B3-spline a trous ("starlet") transform.  The
+ *     reference has no such stage, so the arithmetic is this project's own definition, restated in
+ *     tests/multiscale_model.py.
+ *
+ *     Input.  d [height][width] float32; a NaN or +-inf pixel is a hole; valid(y, x) = inside the image and finite in the input.
+ *       Holes are NaN (0x7fc00000) in every plane and in the output.  1 <= J <= APGPU_STARLET_MAX_SCALES scales.
+ *     Taps.  h = {1, 4, 6, 4, 1} / 16 at offsets (k - 2) s, k = 0 .. 4, spacing s = 2^j for step j = 0 .. J - 1.
+ *     One step, c_j -> c_{j+1} (c_0 = d): normalised convolution; every multiply and add rounds on its own (no contraction).
+ *       Row pass: a(y, x) = sum_k h[k] double(c_j(y, x + (k - 2) s)) and m(y, x) = sum_k h[k], both over the valid taps, k ascending,
+ *       float64, accumulators starting at +0.  Column pass: A(y, x) = sum_k h[k] a(y + (k - 2) s, x) and M(y, x) = sum_k h[k] m(y +
+ *       (k - 2) s, x) over the rows inside the image, k ascending, float64.  c_{j+1}(y, x) = float32(A / M) where valid(y, x), NaN
+ *       elsewhere.  The centre tap of a valid pixel is valid, so M >= 36 / 256: there is no minimum weight.
+ *     Planes.  w_{j+1} = c_j - c_{j+1} in float32.
+ *     Treatment of plane j with the threshold t_j >= 0 (float32): APGPU_STARLET_HARD T(w) = w where |w| >= t, else +0;
+ *       APGPU_STARLET_SOFT T(w) = w - t where w > t, w + t where w < -t, else +0.
+ *     Reconstruction, float32: acc_0 = +0, acc_j = acc_{j-1} + g_j T(w_j), out = acc_J + g_res c_J.
+ *
+ *     The step entry point is one launch: it reads c_in and writes any of c_out = c_{j+1}, w_out = w_{j+1} and acc (NULL: not
+ *       wanted).  With APGPU_STARLET_FIRST acc is written as +0 + gain T(w), otherwise read and added to; with APGPU_STARLET_LAST
+ *       g_res c_{j+1} is added after that.  All planes [height][width] float32 on the device, 4-byte aligned and distinct.  spacing:
+ *       a power of two, 1 .. 32.  form: APGPU_STARLET_FORM_AUTO takes the tile form (a 32 x 64 tile plus a halo of 2 s in LDS) up
+ *       to a spacing of APGPU_STARLET_TILE_MAX_AUTO (0: never, as measured) and the direct form (a lane slides along
+ *       APGPU_STARLET_CHAIN outputs s rows apart, the row sums in registers) above; the other two values force a form, APGPU_EUNSUPPORTED for the tile form above a
+ *       spacing of APGPU_STARLET_TILE_MAX_SPACING.  Both forms give the same bits (csrc/multiscale.hip).
+ *     The plane-1 entry point writes w_1 alone, for the noise estimate (8 bytes per pixel).
+ *     The planes entry point writes w_1 .. w_J and c_J into planes [scales + 1][height][width], J launches.
+ *     The whole-call entry point enqueues J launches and nothing else (no allocation, no host synchronisation): out is the
+ *       accumulator, c_j ping-pongs between the two planes of the workspace, c_J is not stored.  12 bytes per pixel for the first
+ *       step (8 when it is also the last), 16 for the others, 12 for the last.  thresholds_host, gains_host: float32 [scales].
+ *     ws: a workspace of the ws_bytes entry point's size (8 bytes per pixel), 16-byte aligned, owned by the caller; data, out (or
+ *       planes) and ws must not overlap.  APGPU_EINVAL: a NULL plane, planes that are not distinct, a threshold that is negative or
+ *       not finite, a gain that is not finite, scales, spacing, mode, flags or form out of range.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_STARLET_MAX_SCALES 6
+#define APGPU_STARLET_TILE_H 32
+#define APGPU_STARLET_TILE_W 64
+#define APGPU_STARLET_CHAIN 8
+#define APGPU_STARLET_TILE_MAX_SPACING 8   /* the tile form is built for spacings 1, 2, 4, 8 */
+#define APGPU_STARLET_TILE_MAX_AUTO 0      /* the measured switch point: the direct form is faster at every spacing */
+#define APGPU_STARLET_HARD 0
+#define APGPU_STARLET_SOFT 1
+#define APGPU_STARLET_FIRST 1
+#define APGPU_STARLET_LAST 2
+#define APGPU_STARLET_FORM_AUTO 0
+#define APGPU_STARLET_FORM_TILE 1
+#define APGPU_STARLET_FORM_DIRECT 2
+int apgpu_starlet_step_f32(const float *c_in, int64_t height, int64_t width, int32_t spacing, float *c_out, float *w_out, float *acc,
+                           float threshold, float gain, float g_res, int32_t mode, int32_t flags, int32_t form, void *stream);
+int apgpu_starlet_plane1_f32(const float *data, int64_t height, int64_t width, float *w1, void *stream);
+size_t apgpu_starlet_ws_bytes(int64_t height, int64_t width);
+int apgpu_starlet_planes_f32(const float *data, int64_t height, int64_t width, int32_t scales, float *planes, void *ws, size_t ws_bytes,
+                             void *stream);
+int apgpu_multiscale_f32(const float *data, int64_t height, int64_t width, int32_t scales, const float *thresholds_host,
+                         const float *gains_host, float g_res, int32_t mode, float *out, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
