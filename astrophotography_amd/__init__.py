@@ -29,6 +29,7 @@ _LAZY = {
     'ApContinuumSubtract': ('.core.ApContinuumSubtract', 'ApContinuumSubtract'),
     'ApDeconvolve': ('.core.ApDeconvolve', 'ApDeconvolve'),
     'ApMultiscale': ('.core.ApMultiscale', 'ApMultiscale'),
+    'ApDrizzle': ('.core.ApDrizzle', 'ApDrizzle'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

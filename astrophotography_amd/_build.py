@@ -19,7 +19,7 @@ LIB = os.path.join(PKG, 'libapgpu.so')
 # The translation units, in link order.  First the ones that are a source file each ...
 UNITS = ['common', 'elementwise', 'fixbadpix', 'sigclip_global', 'resample', 'resample_stack', 'stack', 'stack_big', 'stack_chunks',
          'stack_mad', 'stack_mad_wide', 'stack_mad_pairs', 'stack_mad_pairs_wide', 'combine_f64', 'background', 'lacosmic', 'autobadcol', 'findstars',
-         'measurestars', 'register', 'composite', 'demosaic', 'continuum', 'deconvolve', 'multiscale']
+         'measurestars', 'register', 'composite', 'demosaic', 'continuum', 'deconvolve', 'multiscale', 'drizzle']
 # ... then the register-resident stack kernels: stack_inst.hip once per slot group x raw dtype x fused calibration (the groups'
 # slot counts: the table in stack_calibrate.h).  The groups are linked in the fatbinary order of the library the recorded
 # measurements were taken with (largest slot counts first): a kernel's place in the loaded code is kept with it.

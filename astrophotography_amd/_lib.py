@@ -29,6 +29,7 @@ STARLET_TILE_MAX_SPACING, STARLET_TILE_MAX_AUTO = 8, 0  # APGPU_STARLET_TILE_MAX
 STARLET_MODE = {'hard': 0, 'soft': 1}                   # APGPU_STARLET_HARD, APGPU_STARLET_SOFT
 STARLET_FIRST, STARLET_LAST = 1, 2                      # APGPU_STARLET_FIRST, APGPU_STARLET_LAST
 STARLET_FORM = {'auto': 0, 'tile': 1, 'direct': 2}      # APGPU_STARLET_FORM_*
+DRIZZLE_TILE_H, DRIZZLE_TILE_W = 4, 64                  # APGPU_DRIZZLE_TILE_H, APGPU_DRIZZLE_TILE_W
 
 
 class ApGpuError(RuntimeError):
@@ -170,6 +171,10 @@ SIGNATURES = {
     'apgpu_starlet_planes_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'apgpu_multiscale_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'apgpu_drizzle_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                    C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'apgpu_drizzle_reject_u8': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

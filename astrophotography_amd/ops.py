@@ -2446,3 +2446,181 @@ def multiscale(image, J=4, k=(3.0, 3.0, 2.0, 1.0), gains=1.0, g_res=1.0, mode='h
     check(_lib.load().apgpu_multiscale_f32(_ptr(image), image.shape[0], image.shape[1], J, t.ctypes.data_as(C.POINTER(C.c_float)),
                                            g.ctypes.data_as(C.POINTER(C.c_float)), float(gr), m, _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out, dict(sigma=sigma, t=t, J=J, mode=mode, k=k, gains=g.astype(np.float64), g_res=float(gr))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F14: ApDrizzle - drizzle co-add of dithered frames and its blot-and-compare rejection (csrc/drizzle.hip; the reference
+# has no such stage: the arithmetic is this project's definition, include/apgpu.h F14, tests/drizzle_model.py)
+DRIZZLE_TILE_H, DRIZZLE_TILE_W = _lib.DRIZZLE_TILE_H, _lib.DRIZZLE_TILE_W
+
+
+def _drizzle_frames(frames):
+    _need_cuda(frames)
+    frames = _f32c(frames, 'frames')
+    if frames.dim() == 2:
+        frames = frames[None]
+    if frames.dim() != 3 or frames.numel() == 0:
+        raise ValueError('frames must be [N,H,W] or [H,W]')
+    return frames
+
+
+def _drizzle_affines(affines, N):
+    a = np.array(torch.as_tensor(affines, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(-1, 6)
+    if a.shape[0] == 1 and N > 1:
+        a = np.repeat(a, N, 0)
+    if a.shape[0] != N:
+        raise ValueError('affines must hold one 2x3 transform per frame')
+    if not np.all(np.isfinite(a)):
+        raise ValueError('the transforms must be finite')
+    return a
+
+
+def _drizzle_f32n(x, N, name, default):
+    """One float32 value per frame (float64 -> float32 as numpy casts), on the host."""
+    if x is None:
+        return np.full(N, default, np.float32)
+    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    x = np.asarray(x, np.float64).reshape(-1)
+    if x.size == 1 and N > 1:
+        x = np.repeat(x, N)
+    if x.size != N:
+        raise ValueError('%s must hold one value per frame' % name)
+    return x.astype(np.float32)
+
+
+def drizzle_out_shape(in_shape, scale):
+    """The default output grid: ceil(scale H) x ceil(scale W), the reference grid at `scale` pixels per pixel."""
+    import math
+    return int(math.ceil(int(in_shape[0]) * float(scale))), int(math.ceil(int(in_shape[1]) * float(scale)))
+
+
+def drizzle_affines(affines, scale):
+    """float64 numpy [N, 6]: the transforms of the grid with `scale` output pixels per reference pixel, output pixel (u, v) at
+    reference coordinate ((u + 0.5) / s - 0.5, (v + 0.5) / s - 0.5): oversampled_affines for any s > 0."""
+    import math
+    s = float(scale)
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError('scale must be a positive number, got %r' % (scale,))
+    a = np.array(affines, dtype=np.float64).reshape(-1, 6)
+    off = 0.5 / s - 0.5
+    fine = a.copy()
+    fine[:, 0] = a[:, 0] / s
+    fine[:, 1] = a[:, 1] / s
+    fine[:, 2] = a[:, 2] + (a[:, 0] + a[:, 1]) * off
+    fine[:, 3] = a[:, 3] / s
+    fine[:, 4] = a[:, 4] / s
+    fine[:, 5] = a[:, 5] + (a[:, 3] + a[:, 4]) * off
+    return fine
+
+
+def _drizzle_mask(m, shape, name, dev):
+    if m is None:
+        return None
+    _need_cuda(m)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError('%s must be [%s]' % (name, ','.join('NHW'[-len(shape):])))
+    return m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)
+
+
+def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, mask=None, frame_masks=None, out_shape=None,
+            conserve_flux=False, cfa=None):
+    """Drizzle co-add (variable-pixel linear reconstruction, "turbo" footprint, gather form) of [N,H,W] float32 frames onto a grid of
+    `scale` output pixels per reference pixel, in one launch (include/apgpu.h F14).
+
+    affines: one 2x3 float64 transform per frame, reference pixel -> input pixel, as resample_affine takes them (ap_register writes
+    them).  pixfrac: the side of a drop in input pixels, (0, 1].  fscale: per-frame flux scale; conserve_flux also multiplies by
+    |det| of the composed transform (surface brightness otherwise).  weights: one finite, positive weight per frame (None: 1).
+    mask [H,W] / frame_masks [N,H,W]: non-zero = bad pixel.  out_shape: (h, w) of the output, default drizzle_out_shape.  cfa:
+    (pattern, channel) - only pixels of that colour feed the plane: pattern as bayer_pattern gives it, channel 0 (R), 1 (G, both
+    greens) or 2 (B).  The footprint of an output pixel must be within (0, 2] input pixels per axis (ValueError).
+
+    Returns dict(image, weight): float32 [h, w]; image NaN and weight 0 where no drop reaches."""
+    import math
+    frames = _drizzle_frames(frames)
+    N, H, W = frames.shape
+    dev = frames.device
+    p = np.float32(pixfrac)
+    if not (p > 0 and p <= 1):
+        raise ValueError('pixfrac must be in (0, 1], got %r' % (pixfrac,))
+    A = drizzle_affines(_drizzle_affines(affines, N), scale)
+    if not np.all(np.isfinite(A)):
+        raise ValueError('the transforms must be finite')
+    hx, hy = 0.5 * np.hypot(A[:, 0], A[:, 3]), 0.5 * np.hypot(A[:, 1], A[:, 4])
+    lx, ly = 2.0 * hx, 2.0 * hy
+    if not (np.all(lx > 0.0) and np.all(lx <= 2.0) and np.all(ly > 0.0) and np.all(ly <= 2.0)):
+        raise ValueError('the footprint of an output pixel must be within (0, 2] input pixels per axis, got %s x %s: '
+                         'use a larger scale' % (lx.tolist(), ly.tolist()))
+    fs = _drizzle_f32n(fscale, N, 'fscale', 1.0)
+    w = _drizzle_f32n(weights, N, 'weights', 1.0)
+    if not np.all(np.isfinite(fs)):
+        raise ValueError('fscale must be finite')
+    if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+        raise ValueError('weights must be finite and positive')
+    g = fs
+    if conserve_flux:
+        g = (fs.astype(np.float64) * np.abs(A[:, 0] * A[:, 4] - A[:, 1] * A[:, 3])).astype(np.float32)
+    if not np.all(np.isfinite(g)):
+        raise ValueError('the flux factors overflow float32')
+    mk = _drizzle_mask(mask, (H, W), 'mask', dev)
+    fm = _drizzle_mask(frame_masks, (N, H, W), 'frame_masks', dev)
+    pat, channel = None, 0
+    if cfa is not None:
+        pattern, channel = cfa
+        pat = (C.c_int32 * 4)(*bayer_pattern(pattern))
+        if isinstance(channel, bool) or int(channel) != channel or int(channel) not in (0, 1, 2):
+            raise ValueError('the cfa channel must be 0 (R), 1 (G) or 2 (B), got %r' % (channel,))
+    h, wo = drizzle_out_shape((H, W), scale) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+    if h < 1 or wo < 1:
+        raise ValueError('out_shape must be positive, got %r' % (out_shape,))
+    prm = np.concatenate([A, hx[:, None], hy[:, None], w.astype(np.float64)[:, None], g.astype(np.float64)[:, None]], 1)
+    prm = torch.from_numpy(np.ascontiguousarray(prm)).to(dev)
+    image = torch.empty((h, wo), dtype=torch.float32, device=dev)
+    weight = torch.empty((h, wo), dtype=torch.float32, device=dev)
+    check(_lib.load().apgpu_drizzle_f32(_ptr(frames), N, H, W, _ptr(mk), _ptr(fm), _ptr(prm), float(p), pat, int(channel), _ptr(image),
+                                        _ptr(weight), h, wo, _stream()))
+    return dict(image=image, weight=weight)
+
+
+def drizzle_reject(frames, affines, ref, ref_scale=1.0, fscale=None, sigmas=None, k=3.5, grow=1.2):
+    """Blot-and-compare outlier flags for drizzle (the driz_cr step): every pixel of every frame is compared with the bilinear value
+    b of the reference image `ref` under it; flagged when |g v - b| > k sigma_i + grow d, d being the spread of the four reference
+    pixels b comes from (it keeps undersampled star cores from being flagged).  ref: float32 [hr, wr] on the grid with `ref_scale`
+    pixels per reference pixel (a median co-add at 1, a first drizzle at its scale), in flux-scaled units.  sigmas: per-frame noise in
+    those units (fscale_i times the frame's clipped standard deviation).  Pixels under which the reference is missing or not finite are not
+    flagged.  Returns uint8 [N, H, W], 1 = outlier: drizzle's frame_masks."""
+    import math
+    frames = _drizzle_frames(frames)
+    N, H, W = frames.shape
+    dev = frames.device
+    _need_cuda(ref)
+    ref = _f32c(ref, 'ref')
+    if ref.dim() != 2 or ref.numel() == 0:
+        raise ValueError('ref must be [hr,wr]')
+    rs = float(ref_scale)
+    if not (math.isfinite(rs) and rs > 0.0):
+        raise ValueError('ref_scale must be a positive number, got %r' % (ref_scale,))
+    kf, gf = np.float32(k), np.float32(grow)
+    if not (np.isfinite(kf) and np.isfinite(gf) and kf >= 0 and gf >= 0):
+        raise ValueError('k and grow must be finite and >= 0, got %r and %r' % (k, grow))
+    a = _drizzle_affines(affines, N)
+    det = a[:, 0] * a[:, 4] - a[:, 1] * a[:, 3]
+    if not np.all(np.isfinite(det)) or np.any(det == 0.0):
+        raise ValueError('a transform is singular')
+    inv = np.empty_like(a)
+    inv[:, 0], inv[:, 1] = a[:, 4] / det, -a[:, 1] / det
+    inv[:, 3], inv[:, 4] = -a[:, 3] / det, a[:, 0] / det
+    inv[:, 2] = -(inv[:, 0] * a[:, 2] + inv[:, 1] * a[:, 5])
+    inv[:, 5] = -(inv[:, 3] * a[:, 2] + inv[:, 4] * a[:, 5])
+    B = inv * rs                                                          # reference coordinate x -> pixel (x + 0.5) rs - 0.5
+    B[:, 2] += 0.5 * rs - 0.5
+    B[:, 5] += 0.5 * rs - 0.5
+    fs = _drizzle_f32n(fscale, N, 'fscale', 1.0)
+    sg = _drizzle_f32n(sigmas, N, 'sigmas', 0.0)
+    if not (np.all(np.isfinite(fs)) and np.all(np.isfinite(sg)) and np.all(sg >= 0)):
+        raise ValueError('fscale must be finite and sigmas finite and >= 0')
+    prm = np.concatenate([B, fs.astype(np.float64)[:, None], sg.astype(np.float64)[:, None]], 1)
+    prm = torch.from_numpy(np.ascontiguousarray(prm)).to(dev)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    check(_lib.load().apgpu_drizzle_reject_u8(_ptr(frames), N, H, W, _ptr(prm), _ptr(ref), ref.shape[0], ref.shape[1], float(kf), float(gf),
+                                              _ptr(out), _stream()))
+    return out

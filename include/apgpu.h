@@ -35,7 +35,8 @@ extern "C" {
                                        apgpu_daofind_convolve_f32, apgpu_local_peaks_f32, apgpu_daofind_measure, apgpu_aperture_phot_f32;
                                        apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match;
                                        apgpu_quantile_levels_f32(_ws_bytes), apgpu_composite_rgb;
-                                       apgpu_bayer_demosaic, apgpu_bayer_channel_sums */
+                                       apgpu_bayer_demosaic, apgpu_bayer_channel_sums;
+                                       apgpu_drizzle_f32, apgpu_drizzle_reject_u8 */
 
 /* error codes */
 #define APGPU_OK            0
@@ -832,6 +833,54 @@ int apgpu_starlet_planes_f32(const float *data, int64_t height, int64_t width, i
                              void *stream);
 int apgpu_multiscale_f32(const float *data, int64_t height, int64_t width, int32_t scales, const float *thresholds_host,
                          const float *gains_host, float g_res, int32_t mode, float *out, void *ws, size_t ws_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F14 ApDrizzle: variable-pixel linear reconstruction ("drizzle", Fruchter & Hook 2002) of N dithered frames onto a finer grid, and
+ *     the blot-and-compare outlier flags in front of it.  The reference has no such stage, so the arithmetic is this project's own
+ *     definition, restated in tests/drizzle_model.py and written once in csrc/drizzle_core.h.  Every multiply and add
+ *     rounds on its own (no contraction).
+ *
+ *     Gather form: per output pixel (u = column, v = row, 0-based, integer = pixel centre), over the frames in order.
+ *     params [n_frames][10] float64 on the device, per frame: A0 .. A5, hx, hy, w, g.
+ *       A maps an OUTPUT pixel to INPUT coordinates, xin = A0 u + A1 v + A2, yin = A3 u + A4 v + A5: the frame's transform composed on
+ *       the host, in float64, with the output grid (output pixel (u, v) at reference coordinate ((u + 0.5) / s - 0.5, (v + 0.5) / s -
+ *       0.5) for `scale` = s output pixels per reference pixel).  hx = 0.5 hypot(A0, A3), hy = 0.5 hypot(A1, A4): the half-widths of
+ *       the "turbo" footprint, the axis-aligned rectangle about (xc, yc) = A(u, v).  The caller keeps lx = 2 hx and ly = 2 hy in
+ *       (0, 2]: with pixfrac <= 1 no overlapping pixel then lies outside the window below (a wider footprint is cut to the window;
+ *       nothing is read out of bounds).  w: the frame's weight, g: its flux factor (fscale, times |det A| when flux is conserved),
+ *       both float32 values, w finite and > 0.
+ *     Float64: xc = (A0 u + A1 v) + A2, yc likewise; x0 = xc - hx, x1 = xc + hx; the window origin i0 = ceil(x0 - p/2), j0 likewise.
+ *       A frame whose window has no pixel on it (i0 outside -3 .. width - 1 or j0 outside -3 .. height - 1, NaN included) adds nothing.
+ *     Float32, in window coordinates: l0 = float(x0 - i0), l1 = float(x1 - i0); the drop of input pixel i0 + t is the square of side
+ *       p = pixfrac about it: ox[t] = max(0, min(l1, t + p/2) - max(l0, t - p/2)), t = 0 .. 3, oy likewise; the cover of tap (ti, tj)
+ *       is a = (ox[ti] oy[tj]) q with q = float32(1 / (double(p) double(p))).
+ *     Taps: rows j0 .. j0 + 3 outer, columns i0 .. i0 + 3 inner.  A tap is skipped when a == 0, the pixel is off the frame, flagged
+ *       in mask [height][width] or in frame_masks [n_frames][height][width] (uint8, non-zero = bad, either may be NULL), not finite, or -
+ *       with a pattern - of another colour: pattern_host [4] holds the colour (R 0, G1 1, B 2, G2 3) of cell position (j & 1) 2 +
+ *       (i & 1) and channel is 0 (R), 1 (G: both greens) or 2 (B); pattern_host NULL: every pixel counts.
+ *     Sums, float64 from +0: aw = a w and gv = g value in float32; den += double(aw); num += double(aw) double(gv) (an exact product).
+ *     image = float32(num / den), NaN (0x7fc00000) where den == 0; weight = float32(den).  Both [out_height][out_width] float32.
+ *     One launch for all frames; a workgroup is APGPU_DRIZZLE_TILE_H rows of APGPU_DRIZZLE_TILE_W output pixels.
+ *
+ *     Rejection, per pixel (c = column, r = row) of frame i with value v.  params [n_frames][8] float64 on the device, per frame:
+ *       B0 .. B5, g, sigma.  B maps an INPUT pixel to the pixel coordinates of ref [ref_height][ref_width] (float32): the inverse of the
+ *       frame's transform composed with the reference image's grid, on the host, in float64.  g as above; sigma: the frame's noise
+ *       in scaled units (float32 values).
+ *     Float64: xr = (B0 c + B1 r) + B2, yr likewise; X = floor(xr), Y = floor(yr).  Float32 from here: fx = float(xr - X), fy likewise;
+ *       p00 = ref[Y][X], p01 = ref[Y][X + 1], p10 = ref[Y + 1][X], p11 = ref[Y + 1][X + 1]; top = p00 + fx (p01 - p00), bot = p10 + fx
+ *       (p11 - p10), b = top + fy (bot - top); d = max of the four - min of the four.
+ *     mask_out[i][r][c] = 1 iff 0 <= X <= ref_width - 2, 0 <= Y <= ref_height - 2, the four and v are finite, and
+ *       |g v - b| > k sigma + grow d (strictly); 0 otherwise.  [n_frames][height][width] uint8.
+ *     APGPU_EINVAL: a NULL plane, a size below 1, pixfrac outside (0, 1], a pattern that is no permutation of 0 .. 3, channel outside
+ *       0 .. 2, image == weight, k or grow negative or not finite.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_DRIZZLE_TILE_H 4
+#define APGPU_DRIZZLE_TILE_W 64
+int apgpu_drizzle_f32(const float *frames, int32_t n_frames, int64_t height, int64_t width, const uint8_t *mask, const uint8_t *frame_masks,
+                      const double *params, float pixfrac, const int32_t *pattern_host, int32_t channel, float *image, float *weight,
+                      int64_t out_height, int64_t out_width, void *stream);
+int apgpu_drizzle_reject_u8(const float *frames, int32_t n_frames, int64_t height, int64_t width, const double *params, const float *ref,
+                            int64_t ref_height, int64_t ref_width, float k, float grow, uint8_t *mask_out, void *stream);
 
 #ifdef __cplusplus
 }
