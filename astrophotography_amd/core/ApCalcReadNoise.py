@@ -54,7 +54,7 @@ class ApImageDifference:
         s = ops.sigclip_global(dev_img, sigma=sigma, maxiters=5).cpu().numpy()
         med, std = float(s[1]), float(s[2])
         lo, hi = med - (sigma * std), med + (sigma * std)
-        f32 = dev_img if dev_img.dtype == torch.float32 else (dev_img.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
+        f32 = dev_img if dev_img.dtype == torch.float32 else _common.widen_u16(dev_img, torch.float32)
         bad, _ = ops.threshold_mask(f32, lo, hi)          # good = (x >= lo) & (x <= hi)  <=>  not (x < lo or x > hi)
         return bad, lo, hi
 

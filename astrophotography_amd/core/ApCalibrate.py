@@ -70,7 +70,7 @@ class ApCalibrate:
         if t.dtype in (torch.float32, torch.float64):
             return t
         if t.dtype == torch.uint16:                       # exact widening
-            return (t.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
+            return _common.widen_u16(t, torch.float32)
         return t.to(torch.float32)
 
     def _read_master(self, path):

@@ -88,11 +88,9 @@ class ApContinuumSubtract:
         if tuple(narrow.shape) != tuple(continuum.shape):
             raise RuntimeError(f'The narrow-band image is {tuple(narrow.shape)} and the continuum image {tuple(continuum.shape)}: '
                                'continuum subtraction needs both on one pixel grid (ap_coadd --center/--pixelscale/--image_size).')
-        import torch
         from .. import ops
         for name, t in (('narrow', narrow), ('continuum', continuum)):
-            if not getattr(t, 'is_cuda', False) or t.dim() != 2 or t.dtype != torch.float32:
-                raise ValueError(f'{name} must be a 2-D float32 CUDA tensor')
+            _common.need_image_f32(t, name)
         keep_matched = self.keep_matched if keep_matched is None else bool(keep_matched)
         xy, peak = self._star_arrays(stars)
         method = self.method or ('stars' if xy is not None else 'pixels')
@@ -169,26 +167,14 @@ class ApContinuumSubtract:
         cols, _, _ = fitsio.read_table(str(path), 'AP_L1MAG')
         return {k: np.asarray(cols[k], np.float64) for k in ('xcenter', 'ycenter', 'peak_adu') if k in cols}
 
-    def _read_image(self, path):
-        import torch
-        _common.check_file_exists(self._logger, path)
-        data, hdr = fitsio.read_device(str(path))
-        if data is None or data.dim() != 2:
-            raise RuntimeError(f'{path}: expected a 2-D primary image.')
-        if data.dtype == torch.uint16:
-            data = (data.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
-        elif data.dtype != torch.float32:
-            data = data.to(torch.float32)
-        return data.contiguous(), hdr
-
     def subtract_files(self, narrow_file, continuum_file, output_file, fwhm=None, stars=None, mask_file=None, scale=None, offset=None,
                        matched_out=None, overwrite=True):
         """FITS in, FITS out (float32).  stars: a source list of ap_find_stars (a file name) or what subtract() takes.  mask_file: a
         FITS image, non-zero = take no part in the fit.  matched_out: a prefix; PREFIX_narrow.fits and PREFIX_continuum.fits get the
         PSF-matched images.  The output header is the narrow-band file's, plus the CSUB* cards and HISTORY.  Returns the report."""
         import torch
-        narrow, hdr = self._read_image(narrow_file)
-        continuum, _ = self._read_image(continuum_file)
+        narrow, hdr = _common.read_image_f32(self._logger, narrow_file)
+        continuum, _ = _common.read_image_f32(self._logger, continuum_file)
         if tuple(narrow.shape) != tuple(continuum.shape):
             raise RuntimeError(f'{narrow_file} is {tuple(narrow.shape)} and {continuum_file} is {tuple(continuum.shape)}: continuum '
                                'subtraction needs both on one pixel grid (ap_coadd --center/--pixelscale/--image_size).')
@@ -196,7 +182,7 @@ class ApContinuumSubtract:
             stars = self.read_star_list(stars)
         mask = None
         if mask_file is not None:
-            m, _ = self._read_image(mask_file)
+            m, _ = _common.read_image_f32(self._logger, mask_file)
             if tuple(m.shape) != tuple(narrow.shape):
                 raise RuntimeError(f'{mask_file} is {tuple(m.shape)}, the images are {tuple(narrow.shape)}.')
             mask = (m != 0).to(torch.uint8)
@@ -204,9 +190,6 @@ class ApContinuumSubtract:
                           keep_matched=self.keep_matched or matched_out is not None)
         rep = r['report']
         out_hdr = hdr.copy()
-        for key in ('BZERO', 'BSCALE'):
-            if key in out_hdr:
-                del out_hdr[key]
 
         def num(v):
             return float(v) if v is not None and math.isfinite(v) else -999.0
@@ -225,12 +208,5 @@ class ApContinuumSubtract:
         names = [(str(output_file), r['image'])]
         if matched_out is not None:
             names += [(f'{matched_out}_narrow.fits', r['narrow_matched']), (f'{matched_out}_continuum.fits', r['continuum_matched'])]
-        pool = fitsio.shared_write_pool()
-        try:
-            for name, plane in names:
-                fitsio.write_device(name, plane, header=out_hdr, overwrite=overwrite, pool=pool)
-        finally:
-            pool.wait()
-        for name, _ in names:
-            self._logger.info(f'Wrote {name}')
+        _common.write_images(self._logger, names, out_hdr, overwrite)
         return rep

@@ -153,7 +153,7 @@ class ApDebayer:
             names = [f'{out_root}_{c}.fits' for c in 'rgb']
             what = 'red, green, blue'
         out_hdr = hdr.copy()
-        for key in ('BZERO', 'BSCALE', 'BAYERPAT', 'XBAYROFF', 'YBAYROFF'):
+        for key in ('BAYERPAT', 'XBAYROFF', 'YBAYROFF'):
             if key in out_hdr:
                 del out_hdr[key]
         out_hdr['DEBAYER'] = (method.upper() if not (grey is not None and luminance_method == 'direct') else 'DIRECT', 'demosaic method')
@@ -163,12 +163,5 @@ class ApDebayer:
         out_hdr['HISTORY'] = f'ApDebayer: {os.path.basename(str(infile))} debayered ({order} in array order, {what})'
         out_hdr['HISTORY'] = ('ApDebayer: black levels ' + (' '.join('%g' % b for b in black) if subtract_black else 'kept')
                               + f', white balance {wb_method if isinstance(wb_method, str) else list(wb_method)}')
-        pool = fitsio.shared_write_pool()
-        try:
-            for plane, name in zip(planes, names):
-                fitsio.write_device(name, plane, header=out_hdr, overwrite=overwrite, pool=pool)
-        finally:
-            pool.wait()
-        for name in names:
-            self._logger.info(f'Wrote {name}')
+        _common.write_images(self._logger, list(zip(names, planes)), out_hdr, overwrite)
         return names

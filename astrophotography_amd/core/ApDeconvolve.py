@@ -92,10 +92,8 @@ class ApDeconvolve:
         start: see ops.richardson_lucy.
 
         Returns dict(image, report)."""
-        import torch
         from .. import ops
-        if not getattr(image, 'is_cuda', False) or image.dim() != 2 or image.dtype != torch.float32:
-            raise ValueError('image must be a 2-D float32 CUDA tensor')
+        _common.need_image_f32(image)
         niter = self.niter if niter is None else int(niter)
         damp = self.damp if damp is None else float(damp)
         readnoise = self.readnoise if readnoise is None else float(readnoise)
@@ -121,22 +119,10 @@ class ApDeconvolve:
         return dict(image=out, report=rep, psf=stamp)
 
     # -- files ---------------------------------------------------------------------------------------------
-    def _read_image(self, path):
-        import torch
-        _common.check_file_exists(self._logger, path)
-        data, hdr = fitsio.read_device(str(path))
-        if data is None or data.dim() != 2:
-            raise RuntimeError(f'{path}: expected a 2-D primary image.')
-        if data.dtype == torch.uint16:
-            data = (data.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
-        elif data.dtype != torch.float32:
-            data = data.to(torch.float32)
-        return data.contiguous(), hdr
-
     def deconvolve_files(self, input_file, output_file, fwhm=None, sky=None, overwrite=True):
         """FITS in, FITS out (float32).  The gain is the header's gain_keyword (1 when it is missing or not positive).  The output
         header is the input's plus the DCON* cards and HISTORY.  Returns the report."""
-        image, hdr = self._read_image(input_file)
+        image, hdr = _common.read_image_f32(self._logger, input_file)
         gain = 1.0
         if self.gain_keyword and self.gain_keyword in hdr:
             try:
@@ -147,9 +133,6 @@ class ApDeconvolve:
         rep = self.deconvolve(image, fwhm=fwhm, sky=sky, gain=gain)
         out, rep = rep['image'], rep['report']
         out_hdr = hdr.copy()
-        for key in ('BZERO', 'BSCALE'):
-            if key in out_hdr:
-                del out_hdr[key]
         name = os.path.basename(self.psf_file) if rep['psf'] == 'file' else rep['psf'].upper()
         out_hdr['DCONPSF'] = (name, 'PSF of the deconvolution')
         out_hdr['DCONFWHM'] = (-999.0 if rep['fwhm'] is None else float(rep['fwhm']), '[pix] FWHM of the PSF')
@@ -160,10 +143,5 @@ class ApDeconvolve:
         out_hdr['DCONSTRT'] = (-999.0 if rep['start'] is None else float(rep['start']), '[adu] start level of the estimate')
         out_hdr['HISTORY'] = (f'ApDeconvolve: {rep["niter"]} Richardson-Lucy iterations, {name} PSF of radius {rep["radius"]}, '
                               f'damping {rep["damp"]:g}, gain {rep["gain"]:g}')
-        pool = fitsio.shared_write_pool()
-        try:
-            fitsio.write_device(str(output_file), out, header=out_hdr, overwrite=overwrite, pool=pool)
-        finally:
-            pool.wait()
-        self._logger.info(f'Wrote {output_file}')
+        _common.write_image(self._logger, output_file, out, out_hdr, overwrite)
         return rep

@@ -152,7 +152,7 @@ class ApFindStars:
         if data_t.dtype == torch.float32:
             d32 = data_t.contiguous()
         elif data_t.dtype == torch.uint16:
-            d32 = (data_t.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
+            d32 = _common.widen_u16(data_t, torch.float32)
         else:
             d32 = data_t.to(torch.float32).contiguous()
         self._data = d32
@@ -175,7 +175,7 @@ class ApFindStars:
         if data_t.dtype == torch.float32:
             x = d32.clone()
         elif data_t.dtype == torch.uint16:
-            x = (data_t.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float64)
+            x = _common.widen_u16(data_t, torch.float64)
         else:
             x = data_t.to(torch.float64)
         x[self._source_mask != 0] = float('nan')

@@ -75,7 +75,7 @@ class ApFixCosmicRays:
         if torch.is_tensor(inpdata):
             data_t = inpdata.cuda()
             if not data_t.dtype.is_floating_point:           # integer frames are widened like the NumPy branch below
-                data_t = (data_t.view(torch.int16).to(torch.int32) & 0xFFFF).double() if data_t.dtype == torch.uint16 else data_t.double()
+                data_t = _common.widen_u16(data_t, torch.float64) if data_t.dtype == torch.uint16 else data_t.double()
         else:
             a = np.ascontiguousarray(inpdata)
             if a.dtype not in (np.float32, np.float64):

@@ -23,7 +23,6 @@ import math
 
 import numpy as np
 
-from .. import fitsio
 from . import _common
 
 MODES = ('hard', 'soft')
@@ -78,10 +77,8 @@ class ApMultiscale:
         it is measured (RuntimeError when the image has no measurable noise: pass sigma).
 
         Returns dict(image, report); report has sigma, t, J, mode, k, gains, g_res, measured."""
-        import torch
         from .. import ops
-        if not getattr(image, 'is_cuda', False) or image.dim() != 2 or image.dtype != torch.float32:
-            raise ValueError('image must be a 2-D float32 CUDA tensor')
+        _common.need_image_f32(image)
         sigma = self.sigma if sigma is None else float(sigma)
         out, rep = ops.multiscale(image, self.scales, self.k, self.gains, self.residual_gain, self.mode, sigma=sigma)
         rep['measured'] = sigma is None
@@ -91,27 +88,12 @@ class ApMultiscale:
         return dict(image=out, report=rep)
 
     # -- files ---------------------------------------------------------------------------------------------
-    def _read_image(self, path):
-        import torch
-        _common.check_file_exists(self._logger, path)
-        data, hdr = fitsio.read_device(str(path))
-        if data is None or data.dim() != 2:
-            raise RuntimeError(f'{path}: expected a 2-D primary image.')
-        if data.dtype == torch.uint16:
-            data = (data.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float32)
-        elif data.dtype != torch.float32:
-            data = data.to(torch.float32)
-        return data.contiguous(), hdr
-
     def process_file(self, input_file, output_file, sigma=None, overwrite=True):
         """FITS in, FITS out (float32).  The output header is the input's plus the MS* cards and HISTORY.  Returns the report."""
-        image, hdr = self._read_image(input_file)
+        image, hdr = _common.read_image_f32(self._logger, input_file)
         rep = self.process(image, sigma=sigma)
         out, rep = rep['image'], rep['report']
         out_hdr = hdr.copy()
-        for key in ('BZERO', 'BSCALE'):
-            if key in out_hdr:
-                del out_hdr[key]
         out_hdr['MSCALES'] = (int(rep['J']), 'starlet scales')
         out_hdr['MSMODE'] = (rep['mode'].upper(), 'thresholding of the starlet planes')
         out_hdr['MSSIGMA'] = (float(rep['sigma']), '[adu] image noise (%s)' % ('measured' if rep['measured'] else 'given'))
@@ -122,10 +104,5 @@ class ApMultiscale:
         out_hdr['MSGRES'] = (float(rep['g_res']), 'gain of the smooth residual')
         out_hdr['HISTORY'] = (f'ApMultiscale: {rep["J"]} starlet scales, {rep["mode"]} thresholds at '
                               f'{",".join("%g" % v for v in rep["k"])} sigma, noise {rep["sigma"]:.6g}')
-        pool = fitsio.shared_write_pool()
-        try:
-            fitsio.write_device(str(output_file), out, header=out_hdr, overwrite=overwrite, pool=pool)
-        finally:
-            pool.wait()
-        self._logger.info(f'Wrote {output_file}')
+        _common.write_image(self._logger, output_file, out, out_hdr, overwrite)
         return rep

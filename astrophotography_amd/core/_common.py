@@ -76,3 +76,47 @@ def remove_pedestal_kw(logger, hdr):
     if 'PEDESTAL' in hdr:
         logger.debug('Removing PEDESTAL keyword from FITS header.')
         del hdr['PEDESTAL']
+
+
+widen_u16 = fitsio.widen_u16                                 # the exact uint16 widening, for the shells
+
+
+def need_image_f32(t, name='image'):
+    """ValueError unless t is a 2-D float32 device tensor."""
+    import torch
+    if not getattr(t, 'is_cuda', False) or t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f'{name} must be a 2-D float32 CUDA tensor')
+
+
+def read_image_f32(logger, path):
+    """The 2-D primary image of a FITS file as a contiguous float32 device tensor (uint16 widened exactly), and its header."""
+    import torch
+    check_file_exists(logger, path)
+    data, hdr = fitsio.read_device(str(path))
+    if data is None or data.dim() != 2:
+        raise RuntimeError(f'{path}: expected a 2-D primary image.')
+    if data.dtype == torch.uint16:
+        data = widen_u16(data, torch.float32)
+    elif data.dtype != torch.float32:
+        data = data.to(torch.float32)
+    return data.contiguous(), hdr
+
+
+def write_images(logger, named, header, overwrite=True):
+    """Writes float device images, (path, tensor) pairs, as FITS files with one header through the shared write pool and waits for
+    them.  The header's BZERO / BSCALE (those of an integer input it was copied from) are dropped, in place."""
+    for key in ('BZERO', 'BSCALE'):
+        if key in header:
+            del header[key]
+    pool = fitsio.shared_write_pool()
+    try:
+        for path, tensor in named:
+            fitsio.write_device(str(path), tensor, header=header, overwrite=overwrite, pool=pool)
+    finally:
+        pool.wait()
+    for path, _ in named:
+        logger.info(f'Wrote {path}')
+
+
+def write_image(logger, path, tensor, header, overwrite=True):
+    write_images(logger, [(path, tensor)], header, overwrite)

@@ -22,6 +22,7 @@
 // (32 + 2 RMAX) (68 + 2 RMAX) 4 + (32 + 2 RMAX) 64 16 bytes, 149 KiB of the 160 KiB of a CU for RMAX = 32 and 52 KiB for RMAX = 4.
 #include "common.h"
 #include "np_exact.h"
+#include "plane_tile.h"
 
 namespace apgpu {
 namespace {
@@ -40,36 +41,16 @@ __global__ __launch_bounds__(kBlock) void gauss_blur_kernel(const float *__restr
                                                            double min_weight, int wide, float *__restrict__ out)
 {
     constexpr int kInH = kTileH + 2 * RMAX;
-    constexpr int kInW = kTileW + 2 * RMAX + 4;            // up to 3 columns of slack left of the halo: the origin is a multiple of 4
+    constexpr int kInW = halo_pitch(kTileW, RMAX);
     __shared__ __attribute__((aligned(16))) float tile[kInH][kInW];
     __shared__ __attribute__((aligned(16))) double2 am[kInH][kTileW];
     __shared__ double wt[2 * RMAX + 1];
     const long long tx0 = (long long)blockIdx.x * kTileW, ty0 = (long long)blockIdx.y * kTileH;
     const int rows = kTileH + 2 * R;                        // staged rows: image rows ty0 - R .. ty0 + kTileH + R - 1
-    const long long gx0 = ((tx0 - R) >> 2) << 2;            // floor to a multiple of 4 (arithmetic shift: negative values too)
-    const int off = (int)(tx0 - R - gx0);                   // 0 .. 3: tile[.][off + j] is image column tx0 - R + j
-    const int cols = (off + kTileW + 2 * R + 3) & ~3;       // staged columns, a multiple of 4 (<= kInW)
-    const float nanv = __uint_as_float(0x7fc00000u);
+    const float nanv = quiet_nan();
 
     if (threadIdx.x <= 2 * R) wt[threadIdx.x] = taps.w[threadIdx.x];
-    const int groups = cols >> 2;
-    for (int idx = threadIdx.x; idx < rows * groups; idx += kBlock) {
-        const int lr = idx / groups, g = idx - lr * groups;
-        const long long gy = ty0 - R + lr, gx = gx0 + 4 * g;
-        float4 v = make_float4(nanv, nanv, nanv, nanv);
-        if (gy >= 0 && gy < H) {
-            const float *row = data + (size_t)gy * (size_t)W;
-            if (wide) {                                     // W is a multiple of 4: a group lies inside the image or outside it
-                if (gx >= 0 && gx < W) v = *reinterpret_cast<const float4 *>(row + gx);
-            } else {
-                if (gx >= 0 && gx < W) v.x = row[gx];
-                if (gx + 1 >= 0 && gx + 1 < W) v.y = row[gx + 1];
-                if (gx + 2 >= 0 && gx + 2 < W) v.z = row[gx + 2];
-                if (gx + 3 >= 0 && gx + 3 < W) v.w = row[gx + 3];
-            }
-        }
-        *reinterpret_cast<float4 *>(&tile[lr][4 * g]) = v;
-    }
+    const int off = stage_halo<kInW, kBlock>(tile, data, H, W, tx0, ty0, kTileW, R, rows, wide);
     __syncthreads();
 
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
@@ -80,14 +61,7 @@ __global__ __launch_bounds__(kBlock) void gauss_blur_kernel(const float *__restr
         double a = 0.0, m = 0.0;
         if (gy >= 0 && gy < H && col_in) {
             const float *p = &tile[lr][off + lane];
-            for (int k = 0; k <= 2 * R; k++) {
-                const float v = p[k];
-                const double w = wt[k];
-                const bool ok = is_finite(v);
-                const double t = w * (double)v;
-                a = ok ? a + t : a;
-                m = ok ? m + w : m;
-            }
+            for (int k = 0; k <= 2 * R; k++) row_add(a, m, p[k], wt[k]);
         }
         am[lr][lane] = make_double2(a, m);
     }
@@ -221,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void pair_moments_kernel(const float *__res
 // ---- the subtraction ----------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float combine1(float x, float y, bool has_y, float ca, float cb, float c0)
 {
-    if (!is_finite(x) || (has_y && !is_finite(y))) return __uint_as_float(0x7fc00000u);
+    if (!is_finite(x) || (has_y && !is_finite(y))) return quiet_nan();
     float v = ca * x;
     if (has_y) v = v + cb * y;
     return v + c0;
@@ -247,8 +221,6 @@ __global__ __launch_bounds__(kBlock) void linear_combine_kernel(const float *x, 
     }
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 inline long long moment_blocks(long long npix)
 {
     const long long b = (((npix + 3) >> 2) + kBlock - 1) / kBlock;
@@ -270,12 +242,11 @@ extern "C" int apgpu_gauss_blur_norm_f32(const float *data, int64_t height, int6
     if (!(min_weight >= 0.0)) return fail(APGPU_EINVAL, "gauss_blur_norm: min_weight %g", min_weight);
     if (data == out) return fail(APGPU_EINVAL, "gauss_blur_norm: out must not be the input");
     if (!aligned(data, 4) || !aligned(out, 4)) return fail(APGPU_EINVAL, "gauss_blur_norm: data and out must be 4-byte aligned");
-    const long long tiles_x = (width + kTileW - 1) / kTileW, tiles_y = (height + kTileH - 1) / kTileH;
-    if (tiles_x > 0x7fffffffLL || tiles_y > 65535) return fail(APGPU_EUNSUPPORTED, "gauss_blur_norm: image of %lld x %lld is too large", (long long)height, (long long)width);
+    dim3 grid;
+    if (int rc = tile_grid("gauss_blur_norm", height, width, kTileH, kTileW, &grid)) return rc;
     BlurTaps t;
     for (int k = 0; k < 2 * kMaxR + 1; k++) t.w[k] = k <= 2 * radius ? taps_host[k] : 0.0;
-    const int wide = aligned(data, 16) && (width & 3) == 0;
-    const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y);
+    const int wide = wide_rows(width, data);
     hipStream_t s = as_stream(stream);
     const long long H = height, W = width;
     if (radius <= 4) hipLaunchKernelGGL((gauss_blur_kernel<4>), grid, dim3(kBlock), 0, s, data, H, W, t, (int)radius, min_weight, wide, out);

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void deconv_update_kernel(const float *__re
             float d[4];
             load4(data, base, xs, W, wide, d);
 #pragma unroll
-            for (int k = 0; k < 4; k++) o[k] = is_finite(d[k]) ? o[k] + sky : __uint_as_float(0x7fc00000u);
+            for (int k = 0; k < 4; k++) o[k] = is_finite(d[k]) ? o[k] + sky : quiet_nan();
         }
         store4(out, base, xs, W, wide, o);
     }
@@ -246,13 +246,11 @@ __global__ __launch_bounds__(kBlock) void deconv_norm_kernel(const float *__rest
         if (out) {
 #pragma unroll
             for (int k = 0; k < 4; k++)
-                o[k] = tile[(ly + R) * G::S + kRun * run + 4 * h + k + R] != 0.0f ? s[k] + sky : __uint_as_float(0x7fc00000u);
+                o[k] = tile[(ly + R) * G::S + kRun * run + 4 * h + k + R] != 0.0f ? s[k] + sky : quiet_nan();
             store4(out, base, xs, W, wide, o);
         }
     }
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 inline size_t plane_bytes(int64_t height, int64_t width) { return (((size_t)height * (size_t)width * sizeof(float)) + 255) & ~(size_t)255; }
 
@@ -272,11 +270,7 @@ int check_common(const char *what, int64_t height, int64_t width, const float *p
     }
     if (!(sum > 0.0)) return fail(APGPU_EINVAL, "%s: the PSF weights sum to %g", what, sum);
     for (int k = 0; k < kMaxK * kMaxK; k++) psf->w[k] = k < n ? psf_host[k] : 0.0f;
-    const long long tiles_x = (width + kTileW - 1) / kTileW, tiles_y = (height + kTileH - 1) / kTileH;
-    if (tiles_x > 0x7fffffffLL || tiles_y > 65535)
-        return fail(APGPU_EUNSUPPORTED, "%s: image of %lld x %lld is too large", what, (long long)height, (long long)width);
-    *grid = dim3((unsigned)tiles_x, (unsigned)tiles_y);
-    return APGPU_OK;
+    return tile_grid(what, height, width, kTileH, kTileW, grid);
 }
 
 #define APGPU_DECONV_RADII(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
@@ -284,7 +278,7 @@ int check_common(const char *what, int64_t height, int64_t width, const float *p
 void launch_norm(int radius, dim3 grid, hipStream_t s, const float *data, long long H, long long W, const Psf &psf, float min_weight,
                  const float *start_plane, float start_level, float sky, float *inv, float *u0, float *out)
 {
-    const int wide = (W & 3) == 0 && aligned(data, 16) && aligned(inv, 16) && aligned(start_plane, 16) && aligned(u0, 16) && aligned(out, 16);
+    const int wide = wide_rows(W, data, inv, start_plane, u0, out);
     switch (radius) {
 #define X(RR) case RR: hipLaunchKernelGGL((deconv_norm_kernel<RR>), grid, dim3(kBlock), 0, s, data, H, W, psf, min_weight, start_plane, start_level, sky, wide, inv, u0, out); break;
         APGPU_DECONV_RADII(X)
@@ -295,7 +289,7 @@ void launch_norm(int radius, dim3 grid, hipStream_t s, const float *data, long l
 void launch_ratio(int radius, dim3 grid, hipStream_t s, const float *u, const float *data, long long H, long long W, const Psf &psf,
                   const RatioArgs &a, float *rout)
 {
-    const int wide = (W & 3) == 0 && aligned(data, 16) && aligned(rout, 16);
+    const int wide = wide_rows(W, data, rout);
     switch (radius) {
 #define X(RR) case RR: hipLaunchKernelGGL((deconv_ratio_kernel<RR>), grid, dim3(kBlock), 0, s, u, data, H, W, psf, a, wide, rout); break;
         APGPU_DECONV_RADII(X)
@@ -306,7 +300,7 @@ void launch_ratio(int radius, dim3 grid, hipStream_t s, const float *u, const fl
 void launch_update(int radius, dim3 grid, hipStream_t s, const float *u, const float *r, const float *inv, const float *data, float sky,
                    long long H, long long W, const Psf &psf, float *out)
 {
-    const int wide = (W & 3) == 0 && aligned(u, 16) && aligned(inv, 16) && aligned(data, 16) && aligned(out, 16);
+    const int wide = wide_rows(W, u, inv, data, out);
     switch (radius) {
 #define X(RR) case RR: hipLaunchKernelGGL((deconv_update_kernel<RR>), grid, dim3(kBlock), 0, s, u, r, inv, data, sky, H, W, psf, wide, out); break;
         APGPU_DECONV_RADII(X)

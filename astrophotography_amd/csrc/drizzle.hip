@@ -80,8 +80,8 @@ extern "C" int apgpu_drizzle_f32(const float *frames, int32_t n_frames, int64_t 
         }
         if (seen != 0xfu) return fail(APGPU_EINVAL, "apgpu_drizzle_f32: the pattern is not a permutation of 0 .. 3");
     }
-    const long long gy = (out_height + kTileH - 1) / kTileH, gx = (out_width + kTileW - 1) / kTileW;
-    if (gy > 65535 || gx > 2147483647LL) return fail(APGPU_EUNSUPPORTED, "apgpu_drizzle_f32: output %lld x %lld is too large", (long long)out_height, (long long)out_width);
+    dim3 grid;
+    if (int rc = tile_grid("apgpu_drizzle_f32", out_height, out_width, kTileH, kTileW, &grid)) return rc;
     DrizzleImage im;
     im.frames = frames;
     im.mask = mask;
@@ -91,7 +91,7 @@ extern "C" int apgpu_drizzle_f32(const float *frames, int32_t n_frames, int64_t 
     im.hp = 0.5f * pixfrac;
     im.q = (float)(1.0 / ((double)pixfrac * (double)pixfrac));
     im.cfa = cfa;
-    hipLaunchKernelGGL(drizzle_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(kTileW, kTileH), 0, as_stream(stream), im, n_frames, params, image, weight,
+    hipLaunchKernelGGL(drizzle_kernel, grid, dim3(kTileW, kTileH), 0, as_stream(stream), im, n_frames, params, image, weight,
                        (long long)out_height, (long long)out_width);
     return check_launch("drizzle_kernel");
 }

@@ -77,7 +77,7 @@ APGPU_HD inline void drizzle_frame(const DrizzleImage &im, long long f, const do
 
 APGPU_HD inline void drizzle_finish(double num, double den, float &image, float &weight)
 {
-    image = den == 0.0 ? bits_as<float>(0x7fc00000u) : (float)(num / den);
+    image = den == 0.0 ? quiet_nan() : (float)(num / den);
     weight = (float)den;
 }
 

@@ -515,8 +515,6 @@ __global__ __launch_bounds__(kBlock) void fits_swap64_kernel(const unsigned long
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = __builtin_bswap64(in[i]);
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 // =================================================================================================
@@ -527,7 +525,7 @@ extern "C" int apgpu_calibrate(const void *raw, int raw_dtype, const float *bias
     if (!raw || !bias || !dark || !exp_ratio || !out) return fail(APGPU_EINVAL, "calibrate: NULL pointer argument");
     if (n_frames <= 0 || n_pixels <= 0) return fail(APGPU_EINVAL, "calibrate: empty slab (%lld x %lld)", (long long)n_frames, (long long)n_pixels);
     if (raw_dtype != APGPU_F32 && raw_dtype != APGPU_U16) return fail(APGPU_EINVAL, "calibrate: bad raw dtype %d", raw_dtype);
-    if (!aligned16(raw) || !aligned16(bias) || !aligned16(dark) || !aligned16(out) || (nflat && !aligned16(nflat)))
+    if (!aligned(raw, 16) || !aligned(bias, 16) || !aligned(dark, 16) || !aligned(out, 16) || (nflat && !aligned(nflat, 16)))
         return fail(APGPU_EINVAL, "calibrate: buffers must be 16-byte aligned");
     const int vec = (n_pixels % 4) == 0 || n_frames == 1;
     const unsigned grid = grid_for(vec ? (n_pixels + 3) / 4 : n_frames * n_pixels);
@@ -603,7 +601,7 @@ static int flat_normalize_impl(const T *flat, T *nflat, T *norm_out, int64_t n_p
 {
     if (!flat || !norm_out || !ws) return fail(APGPU_EINVAL, "flat_normalize: NULL pointer argument");
     if (n_pixels <= 0) return fail(APGPU_EINVAL, "flat_normalize: n_pixels = %lld", (long long)n_pixels);
-    if (!aligned16(flat) || (nflat && !aligned16(nflat)) || !aligned16(ws)) return fail(APGPU_EINVAL, "flat_normalize: buffers must be 16-byte aligned");
+    if (!aligned(flat, 16) || (nflat && !aligned(nflat, 16)) || !aligned(ws, 16)) return fail(APGPU_EINVAL, "flat_normalize: buffers must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     unsigned long long *nan_count = static_cast<unsigned long long *>(ws);
     T *piece_sums = reinterpret_cast<T *>(static_cast<char *>(ws) + 16);
@@ -632,7 +630,7 @@ extern "C" int apgpu_threshold_mask_f32(const float *data, int64_t n_pixels, dou
 {
     if (!data || !mask || !nbad_out) return fail(APGPU_EINVAL, "threshold_mask: NULL pointer argument");
     if (n_pixels <= 0) return fail(APGPU_EINVAL, "threshold_mask: n_pixels = %lld", (long long)n_pixels);
-    if (!aligned16(data) || !aligned16(mask)) return fail(APGPU_EINVAL, "threshold_mask: buffers must be 16-byte aligned");
+    if (!aligned(data, 16) || !aligned(mask, 16)) return fail(APGPU_EINVAL, "threshold_mask: buffers must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(nbad_out, 0, sizeof(int64_t), st) != hipSuccess) return fail(APGPU_ELAUNCH, "threshold_mask: memset failed");
     hipLaunchKernelGGL(threshold_mask_kernel, dim3(grid_for(n_pixels / 16 + 1)), dim3(kBlock), 0, st, data, n_pixels, lothresh,
@@ -686,7 +684,7 @@ extern "C" int apgpu_imarith(const void *a, const void *b, double scalar, int op
     hipStream_t st = as_stream(stream);
     const unsigned grid = grid_for(n_pixels / 4 + 1);
     if (dtype == APGPU_F32) {
-        if (!aligned16(a) || !aligned16(out) || (b && !aligned16(b))) return fail(APGPU_EINVAL, "imarith: buffers must be 16-byte aligned");
+        if (!aligned(a, 16) || !aligned(out, 16) || (b && !aligned(b, 16))) return fail(APGPU_EINVAL, "imarith: buffers must be 16-byte aligned");
         const float *fa = (const float *)a, *fb = (const float *)b;
         float *fo = (float *)out;
         const float s = (float)scalar;
@@ -732,7 +730,7 @@ extern "C" int apgpu_fits_decode(const void *payload, int bitpix, int unsigned16
 {
     if (!payload || !out) return fail(APGPU_EINVAL, "fits_decode: NULL pointer argument");
     if (n_pixels <= 0) return fail(APGPU_EINVAL, "fits_decode: n_pixels = %lld", (long long)n_pixels);
-    if (!aligned16(payload) || !aligned16(out)) return fail(APGPU_EINVAL, "fits_decode: buffers must be 16-byte aligned");
+    if (!aligned(payload, 16) || !aligned(out, 16)) return fail(APGPU_EINVAL, "fits_decode: buffers must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (bitpix == 16 && unsigned16) {
         const int64_t nwords = n_pixels / 2;
@@ -758,7 +756,7 @@ extern "C" int apgpu_fits_encode_f32(const float *data, void *payload, int64_t n
 {
     if (!data || !payload) return fail(APGPU_EINVAL, "fits_encode: NULL pointer argument");
     if (n_pixels <= 0) return fail(APGPU_EINVAL, "fits_encode: n_pixels = %lld", (long long)n_pixels);
-    if (!aligned16(data) || !aligned16(payload)) return fail(APGPU_EINVAL, "fits_encode: buffers must be 16-byte aligned");
+    if (!aligned(data, 16) || !aligned(payload, 16)) return fail(APGPU_EINVAL, "fits_encode: buffers must be 16-byte aligned");
     hipLaunchKernelGGL(fits_swap32_kernel, dim3(grid_for(n_pixels / 4 + 1)), dim3(kBlock), 0, as_stream(stream),
                        (const unsigned *)data, (unsigned *)payload, n_pixels);
     return check_launch("fits_encode");
@@ -768,7 +766,7 @@ extern "C" int apgpu_fits_encode_f64(const double *data, void *payload, int64_t 
 {
     if (!data || !payload) return fail(APGPU_EINVAL, "fits_encode_f64: NULL pointer argument");
     if (n_pixels <= 0) return fail(APGPU_EINVAL, "fits_encode_f64: n_pixels = %lld", (long long)n_pixels);
-    if (!aligned16(data) || !aligned16(payload)) return fail(APGPU_EINVAL, "fits_encode_f64: buffers must be 16-byte aligned");
+    if (!aligned(data, 16) || !aligned(payload, 16)) return fail(APGPU_EINVAL, "fits_encode_f64: buffers must be 16-byte aligned");
     hipLaunchKernelGGL(fits_swap64_kernel, dim3(grid_for(n_pixels)), dim3(kBlock), 0, as_stream(stream),
                        (const unsigned long long *)data, (unsigned long long *)payload, n_pixels);
     return check_launch("fits_encode_f64");

@@ -26,6 +26,7 @@
 // Rows outside the image enter the column sums as (a, m) = (+0, +0): h 0 = +0 leaves an accumulator (never -0) as it is, as skipping does.
 #include "common.h"
 #include "np_exact.h"
+#include "plane_tile.h"
 
 namespace apgpu {
 namespace {
@@ -43,19 +44,11 @@ struct StepScalars {
 
 __device__ __forceinline__ double tap(int k) { return k == 2 ? 0.375 : (k == 1 || k == 3 ? 0.25 : 0.0625); }
 
-__device__ __forceinline__ void row_add(double &a, double &m, float v, double w)
-{
-    const bool ok = is_finite(v);
-    const double t = w * (double)v;
-    a = ok ? a + t : a;
-    m = ok ? m + w : m;
-}
-
 // One output pixel: c is c_j there, (A, M) the column sums.
 __device__ __forceinline__ void emit(float *__restrict__ c_out, float *__restrict__ w_out, float *__restrict__ acc, const StepScalars &p, size_t idx,
                                      float c, double A, double M)
 {
-    const float nanv = __uint_as_float(0x7fc00000u);
+    const float nanv = quiet_nan();
     const bool ok = is_finite(c);
     const float cn = ok ? (float)(A / M) : nanv;
     if (c_out) c_out[idx] = cn;
@@ -78,34 +71,12 @@ __global__ __launch_bounds__(kBlock) void starlet_tile_kernel(const float *__res
 {
     constexpr int R = 2 * S;
     constexpr int kInH = kTileH + 2 * R;
-    constexpr int kInW = kTileW + 2 * R + 4;                // up to 3 columns of slack left of the halo: the origin is a multiple of 4
+    constexpr int kInW = halo_pitch(kTileW, R);
     __shared__ __attribute__((aligned(16))) float tile[kInH][kInW];
     __shared__ double sa[kInH][kTileW];
     __shared__ float sm[kInH][kTileW];                      // a sum of sixteenths, at most 1: exact in float32
     const long long tx0 = (long long)blockIdx.x * kTileW, ty0 = (long long)blockIdx.y * kTileH;
-    const long long gx0 = ((tx0 - R) >> 2) << 2;            // floor to a multiple of 4 (arithmetic shift: negative values too)
-    const int off = (int)(tx0 - R - gx0);                   // 0 .. 3: tile[.][off + j] is image column tx0 - R + j
-    const int cols = (off + kTileW + 2 * R + 3) & ~3;       // staged columns, a multiple of 4 (<= kInW)
-    const float nanv = __uint_as_float(0x7fc00000u);
-
-    const int groups = cols >> 2;
-    for (int idx = threadIdx.x; idx < kInH * groups; idx += kBlock) {
-        const int lr = idx / groups, g = idx - lr * groups;
-        const long long gy = ty0 - R + lr, gx = gx0 + 4 * g;
-        float4 v = make_float4(nanv, nanv, nanv, nanv);
-        if (gy >= 0 && gy < H) {
-            const float *row = in + (size_t)gy * (size_t)W;
-            if (wide) {                                     // W is a multiple of 4: a group lies inside the image or outside it
-                if (gx >= 0 && gx < W) v = *reinterpret_cast<const float4 *>(row + gx);
-            } else {
-                if (gx >= 0 && gx < W) v.x = row[gx];
-                if (gx + 1 >= 0 && gx + 1 < W) v.y = row[gx + 1];
-                if (gx + 2 >= 0 && gx + 2 < W) v.z = row[gx + 2];
-                if (gx + 3 >= 0 && gx + 3 < W) v.w = row[gx + 3];
-            }
-        }
-        *reinterpret_cast<float4 *>(&tile[lr][4 * g]) = v;
-    }
+    const int off = stage_halo<kInW, kBlock>(tile, in, H, W, tx0, ty0, kTileW, R, kInH, wide);
     __syncthreads();
 
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
@@ -148,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void starlet_direct_kernel(const float *__r
     const long long q = (long long)blockIdx.y / s, rho = (long long)blockIdx.y - q * s;
     const long long y0 = q * s * kChain + rho;
     if (y0 >= H) return;
-    const float nanv = __uint_as_float(0x7fc00000u);
+    const float nanv = quiet_nan();
     long long xo[5];
     bool xin[5];
 #pragma unroll
@@ -198,32 +169,22 @@ __global__ __launch_bounds__(kBlock) void starlet_direct_kernel(const float *__r
     }
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline bool finite_f(float x) { return is_finite(x); }
 
 inline size_t plane_stride(int64_t height, int64_t width) { return ((size_t)height * (size_t)width + 3) & ~(size_t)3; }
-
-int check_image(const char *what, const float *data, int64_t height, int64_t width)
-{
-    if (!data) return fail(APGPU_EINVAL, "%s: NULL pointer argument", what);
-    if (height <= 0 || width <= 0) return fail(APGPU_EINVAL, "%s: image of %lld x %lld", what, (long long)height, (long long)width);
-    if (!aligned(data, 4)) return fail(APGPU_EINVAL, "%s: the planes must be 4-byte aligned", what);
-    return APGPU_OK;
-}
 
 // One launch.  The planes are distinct and 4-byte aligned, spacing is a power of two <= kMaxSpacing: the callers have checked.
 int launch_step(const char *what, const float *in, int64_t height, int64_t width, int spacing, float *c_out, float *w_out, float *acc,
                 const StepScalars &p, int form, hipStream_t st)
 {
     const long long H = height, W = width;
+    dim3 grid;
     if (form == APGPU_STARLET_FORM_AUTO) form = spacing <= APGPU_STARLET_TILE_MAX_AUTO ? APGPU_STARLET_FORM_TILE : APGPU_STARLET_FORM_DIRECT;
     if (form == APGPU_STARLET_FORM_TILE) {
         if (spacing > APGPU_STARLET_TILE_MAX_SPACING)
             return fail(APGPU_EUNSUPPORTED, "%s: the tile form holds a spacing of %d, got %d", what, APGPU_STARLET_TILE_MAX_SPACING, spacing);
-        const long long tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
-        if (tiles_x > 0x7fffffffLL || tiles_y > 65535) return fail(APGPU_EUNSUPPORTED, "%s: image of %lld x %lld is too large", what, H, W);
-        const int wide = aligned(in, 16) && (W & 3) == 0;
-        const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y);
+        if (int rc = tile_grid(what, H, W, kTileH, kTileW, &grid)) return rc;
+        const int wide = wide_rows(W, in);
         if (spacing == 1) hipLaunchKernelGGL((starlet_tile_kernel<1>), grid, dim3(kBlock), 0, st, in, c_out, w_out, acc, H, W, wide, p);
         else if (spacing == 2) hipLaunchKernelGGL((starlet_tile_kernel<2>), grid, dim3(kBlock), 0, st, in, c_out, w_out, acc, H, W, wide, p);
         else if (spacing == 4) hipLaunchKernelGGL((starlet_tile_kernel<4>), grid, dim3(kBlock), 0, st, in, c_out, w_out, acc, H, W, wide, p);
@@ -231,9 +192,8 @@ int launch_step(const char *what, const float *in, int64_t height, int64_t width
     } else {
         const long long blocks_x = (W + kBlock - 1) / kBlock;
         const long long chains = (H + (long long)spacing * kChain - 1) / ((long long)spacing * kChain) * spacing;
-        if (blocks_x > 0x7fffffffLL || chains > 65535) return fail(APGPU_EUNSUPPORTED, "%s: image of %lld x %lld is too large", what, H, W);
-        hipLaunchKernelGGL(starlet_direct_kernel, dim3((unsigned)blocks_x, (unsigned)chains), dim3(kBlock), 0, st, in, c_out, w_out, acc, H, W,
-                           spacing, p);
+        if (int rc = launch_grid(what, H, W, blocks_x, chains, &grid)) return rc;
+        hipLaunchKernelGGL(starlet_direct_kernel, grid, dim3(kBlock), 0, st, in, c_out, w_out, acc, H, W, spacing, p);
     }
     return check_launch(what);
 }
@@ -246,7 +206,7 @@ using namespace apgpu;
 extern "C" int apgpu_starlet_step_f32(const float *c_in, int64_t height, int64_t width, int32_t spacing, float *c_out, float *w_out, float *acc,
                                       float threshold, float gain, float g_res, int32_t mode, int32_t flags, int32_t form, void *stream)
 {
-    if (int rc = check_image("starlet_step", c_in, height, width)) return rc;
+    if (int rc = check_plane("starlet_step", c_in, height, width)) return rc;
     if (!c_out && !w_out && !acc) return fail(APGPU_EINVAL, "starlet_step: no output plane");
     if (spacing < 1 || spacing > kMaxSpacing || (spacing & (spacing - 1)))
         return fail(APGPU_EINVAL, "starlet_step: spacing %d is not a power of two from 1 to %d", spacing, kMaxSpacing);
@@ -270,7 +230,7 @@ extern "C" size_t apgpu_starlet_ws_bytes(int64_t height, int64_t width)
 
 extern "C" int apgpu_starlet_plane1_f32(const float *data, int64_t height, int64_t width, float *w1, void *stream)
 {
-    if (int rc = check_image("starlet_plane1", data, height, width)) return rc;
+    if (int rc = check_plane("starlet_plane1", data, height, width)) return rc;
     if (!w1 || w1 == data || !aligned(w1, 4)) return fail(APGPU_EINVAL, "starlet_plane1: w1 must be a 4-byte aligned plane distinct from the input");
     const StepScalars p = {0.0f, 1.0f, 1.0f, 0, 1, 0};
     return launch_step("starlet_plane1", data, height, width, 1, nullptr, w1, nullptr, p, APGPU_STARLET_FORM_AUTO, as_stream(stream));
@@ -279,7 +239,7 @@ extern "C" int apgpu_starlet_plane1_f32(const float *data, int64_t height, int64
 static int check_ws(const char *what, const float *data, int64_t height, int64_t width, int32_t scales, const float *out, size_t out_planes,
                     const void *ws, size_t ws_bytes)
 {
-    if (int rc = check_image(what, data, height, width)) return rc;
+    if (int rc = check_plane(what, data, height, width)) return rc;
     if (!out || !ws) return fail(APGPU_EINVAL, "%s: NULL pointer argument", what);
     if (scales < 1 || scales > APGPU_STARLET_MAX_SCALES) return fail(APGPU_EINVAL, "%s: %d scales, 1 to %d are built", what, scales, APGPU_STARLET_MAX_SCALES);
     if (!aligned(out, 4) || !aligned(ws, 16)) return fail(APGPU_EINVAL, "%s: out must be 4-byte aligned, ws 16-byte aligned", what);

@@ -62,6 +62,8 @@ APGPU_HD inline bool is_finite(const double &x)
 {
     return (bits_as<unsigned long long>(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }
+// the NaN that marks a pixel without data in every float32 output: quiet, positive, no payload
+APGPU_HD inline float quiet_nan() { return bits_as<float>(0x7fc00000u); }
 
 // numpy's sum of n <= 128 terms f(0) .. f(n - 1).  The index is 64-bit so that f(i + k) over an array is base + constant
 // and the eight loads of a round stay one or two wide loads, as in a loop over a pointer.  The round loop is kept rolled:

@@ -36,6 +36,12 @@ class Card:
         return 'Card(%r, %r, %r)' % (self.key, self.value, self.comment)
 
 
+def widen_u16(t, dtype):
+    """A torch.uint16 tensor as `dtype`, exactly (torch has no uint16 arithmetic: the bits are read as int16 and the sign undone)."""
+    import torch
+    return (t.view(torch.int16).to(torch.int32) & 0xFFFF).to(dtype)
+
+
 def _parse_value(s):
     """Value/comment field (columns 11-80) of a FITS card -> (value, comment)."""
     s = s.rstrip()
@@ -796,7 +802,7 @@ def read_slab_device(paths, device='cuda', dtype='auto', timings=None):
                                                  count, C.c_void_p(cs.cuda_stream)))
                 if not direct:
                     if ddt == torch.uint16 and sdt != torch.uint16:      # widen exactly (torch has no uint16 arithmetic)
-                        dst = dst.view(torch.int16).to(torch.int32) & 0xFFFF
+                        dst = widen_u16(dst, torch.int32)
                     if sdt == torch.uint16:
                         slab[k].view(torch.int16).copy_(dst.view(torch.int16))
                     else:

@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import APGPU_F32, APGPU_F64, APGPU_U16, StackArgs, check
+from .fitsio import widen_u16
 
 
 def _stream():
@@ -41,6 +42,56 @@ def _f32c(t, name):
     if t.dtype != torch.float32:
         raise TypeError('%s must be float32, got %s' % (name, t.dtype))
     return t.contiguous()
+
+
+def _image_f32(data, name='data'):
+    """A non-empty 2-D float32 device image, contiguous."""
+    _need_cuda(data)
+    data = _f32c(data, name)
+    if data.dim() != 2 or data.numel() == 0:
+        raise ValueError('%s must be a non-empty 2-D image, got shape %s' % (name, tuple(data.shape)))
+    return data
+
+
+def _plane_like(t, name, like):
+    """... of the shape of `like`."""
+    t = _image_f32(t, name)
+    if tuple(t.shape) != tuple(like.shape):
+        raise ValueError('%s must have the image shape %s, got %s' % (name, tuple(like.shape), tuple(t.shape)))
+    return t
+
+
+def _out_f32(out, like, *distinct, shape=None, name='out'):
+    """An output argument: None (a new tensor of `shape`, that of `like` unless given), or a contiguous float32 device tensor of
+    that shape that is none of `distinct`."""
+    if out is None:
+        return torch.empty_like(like) if shape is None else torch.empty(shape, dtype=torch.float32, device=like.device)
+    shape = tuple(like.shape if shape is None else shape)
+    _need_cuda(out)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or \
+            any(out.data_ptr() == t.data_ptr() for t in distinct):
+        raise ValueError('%s must be a contiguous float32 device tensor of shape %s%s' % (name, shape, ', distinct from the input planes' if distinct else ''))
+    return out
+
+
+def _workspace(ws, need, device, maker):
+    """A workspace argument: None (a new one), or a contiguous, 16-byte aligned uint8 device tensor of at least `need` bytes."""
+    if ws is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    _need_cuda(ws)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
+        raise ValueError('ws must be a contiguous, 16-byte aligned uint8 device tensor of at least %d bytes (ops.%s)' % (need, maker))
+    return ws
+
+
+def _mask_u8(mask, shape, message, error=ValueError):
+    """A mask argument: None, or a device tensor of `shape` as contiguous uint8 (another dtype: != 0)."""
+    if mask is None:
+        return None
+    _need_cuda(mask)
+    if tuple(mask.shape) != tuple(shape):
+        raise error(message)
+    return (mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)).contiguous()
 
 
 def _raw_dtype(t):
@@ -529,7 +580,7 @@ def sigclip_global(data, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters
     else:
         f64 = True
         if data.dtype == torch.uint16:
-            data = (data.view(torch.int16).to(torch.int32) & 0xFFFF).to(torch.float64)
+            data = widen_u16(data, torch.float64)
         else:
             data = data.to(torch.float64)
         data = data.contiguous()
@@ -688,10 +739,8 @@ def fix_badpix(data, mask, deltapix=1, min_valid=4):
     data = data.contiguous() if f64 else _f32c(data, 'data')
     if data.dim() != 2:
         raise ValueError('data must be 2-D')
-    if tuple(mask.shape) != tuple(data.shape):
-        raise RuntimeError('Error, the shape of the input data array (%s) does not match that of the bad pixel '
-                           'mask array (%s).' % (tuple(data.shape), tuple(mask.shape)))
-    m8 = (mask != 0).to(torch.uint8).contiguous() if mask.dtype != torch.uint8 else mask.contiguous()
+    m8 = _mask_u8(mask, data.shape, 'Error, the shape of the input data array (%s) does not match that of the bad pixel '
+                  'mask array (%s).' % (tuple(data.shape), tuple(mask.shape)), RuntimeError)
     out = torch.empty_like(data)
     stats = torch.empty(3, dtype=torch.int64, device=data.device)
     fn = _lib.load().apgpu_fix_badpix_f64 if f64 else _lib.load().apgpu_fix_badpix_f32
@@ -824,12 +873,7 @@ def _resample_args(frames, affines, fscale, mask, out_shape, n_phases):
         if fs.numel() != N:
             raise ValueError('fscale must hold one value per frame')
         fs = fs.contiguous().to(dev)
-    mk = None
-    if mask is not None:
-        _need_cuda(mask)
-        if tuple(mask.shape) != (H, W):
-            raise ValueError('mask must be [H,W]')
-        mk = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    mk = _mask_u8(mask, (H, W), 'mask must be [H,W]')
     return frames, N, H, W, h, w, aff, per_tile, fs, mk, lanczos3_table(n_phases, dev)
 
 
@@ -991,12 +1035,7 @@ def resample_oversampled(frames, affines, oversampling, fscale=None, mask=None, 
     frames, N, H, W, n, h, w, fine_aff, fs = _oversampling_args(frames, affines, oversampling, fscale, out_shape, conserve_flux,
                                                                  fine_affines, int(oversampling))
     dev = frames.device
-    mk = None
-    if mask is not None:
-        _need_cuda(mask)
-        if tuple(mask.shape) != (H, W):
-            raise ValueError('mask must be [H,W]')
-        mk = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    mk = _mask_u8(mask, (H, W), 'mask must be [H,W]')
     fine_aff = fine_aff.contiguous().to(dev)
     fs = fs.contiguous().to(dev)
     lut = lanczos3_table(n_phases, dev)
@@ -1277,14 +1316,6 @@ def _kernel_on(kernel, device):
     return kernel
 
 
-def _image_f32(data, name='data'):
-    _need_cuda(data)
-    data = _f32c(data, name)
-    if data.dim() != 2 or data.numel() == 0:
-        raise ValueError('%s must be a non-empty 2-D image, got shape %s' % (name, tuple(data.shape)))
-    return data
-
-
 def daofind_convolve(data, kernel, bg_median=0.0):
     """float32 image [H, W] -> the image convolved with the DAOFIND kernel (daofind_kernel(fwhm) or a fwhm), float32:
     d = data - float32(bg_median) inside the image, 0 outside; float64 accumulation over all taps in row-major tap order."""
@@ -1316,11 +1347,7 @@ def local_peaks(values, footprint, threshold, mask=None, border=0, capacity=4096
         fp = torch.from_numpy(np.ascontiguousarray((np.asarray(footprint) != 0).astype(np.uint8))).to(dev)
     if fp.dim() != 2:
         raise ValueError('footprint must be 2-D')
-    if mask is not None:
-        _need_cuda(mask)
-        if tuple(mask.shape) != tuple(values.shape):
-            raise ValueError('mask must have the image shape')
-        mask = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    mask = _mask_u8(mask, values.shape, 'mask must have the image shape')
     capacity = int(capacity)
     if list_out is None:
         list_out = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
@@ -1930,10 +1957,7 @@ def gauss_blur(data, sigma, min_weight=0.5, out=None):
         raise ValueError('a blur radius of %d, the kernel holds %d' % (R, BLUR_MAX_RADIUS))
     if not float(min_weight) >= 0.0:
         raise ValueError('min_weight must be >= 0, got %r' % (min_weight,))
-    if out is None:
-        out = torch.empty_like(data)
-    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(data.shape) or not out.is_contiguous() or out.data_ptr() == data.data_ptr():
-        raise ValueError('out must be a contiguous float32 device tensor of the image shape, distinct from the input')
+    out = _out_f32(out, data, data)
     check(_lib.load().apgpu_gauss_blur_norm_f32(_ptr(data), data.shape[0], data.shape[1], taps.ctypes.data_as(C.POINTER(C.c_double)), R,
                                                 float(min_weight), _ptr(out), _stream()))
     return out
@@ -1943,12 +1967,7 @@ def _pair(n, c, mask=None):
     n, c = _image_f32(n, 'n'), _image_f32(c, 'c')
     if tuple(n.shape) != tuple(c.shape):
         raise ValueError('the two images must have one shape, got %s and %s' % (tuple(n.shape), tuple(c.shape)))
-    if mask is not None:
-        _need_cuda(mask)
-        if tuple(mask.shape) != tuple(n.shape):
-            raise ValueError('mask must have the image shape')
-        mask = mask.contiguous() if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
-    return n, c, mask
+    return n, c, _mask_u8(mask, n.shape, 'mask must have the image shape')
 
 
 def pair_moments(n, c, s=0.0, b=0.0, lo=-float('inf'), hi=float('inf'), mask=None, ws=None):
@@ -1974,10 +1993,7 @@ def linear_combine(x, y, ca, cb, c0, out=None):
     y = _f32c(y, 'y')
     if x.numel() == 0 or (y is not None and tuple(y.shape) != tuple(x.shape)):
         raise ValueError('x and y must be non-empty tensors of one shape')
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float32 device tensor of the shape of x')
+    out = _out_f32(out, x)
     check(_lib.load().apgpu_linear_combine_f32(_ptr(x), _ptr(y), float(np.float32(ca)), float(np.float32(cb)), float(np.float32(c0)), _ptr(out),
                                                x.numel(), _stream()))
     return out
@@ -2195,28 +2211,11 @@ def _psf_arg(p):
     return p.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _deconv_plane(t, name, like):
-    t = _image_f32(t, name)
-    if tuple(t.shape) != tuple(like.shape):
-        raise ValueError('%s must have the image shape %s, got %s' % (name, tuple(like.shape), tuple(t.shape)))
-    return t
-
-
-def _deconv_out(out, like, *distinct):
-    if out is None:
-        return torch.empty_like(like)
-    _need_cuda(out)
-    if out.dtype != torch.float32 or tuple(out.shape) != tuple(like.shape) or not out.is_contiguous() or \
-            any(out.data_ptr() == t.data_ptr() for t in distinct):
-        raise ValueError('out must be a contiguous float32 device tensor of the image shape, distinct from the plane under the taps')
-    return out
-
-
 def deconv_norm(data, psf, min_weight=0.1, out=None):
     """Step 1 of F12: inv = 1 / n where n = sum p W >= min_weight (W = 1 at the finite pixels), else 0."""
     data = _image_f32(data)
     p, R = psf_stamp(psf)
-    out = _deconv_out(out, data, data)
+    out = _out_f32(out, data, data)
     check(_lib.load().apgpu_deconv_norm_f32(_ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(min_weight), _ptr(out), _stream()))
     return out
 
@@ -2224,9 +2223,9 @@ def deconv_norm(data, psf, min_weight=0.1, out=None):
 def deconv_ratio(u, data, psf, sky, gain=1.0, readnoise=0.0, damp=0.0, out=None):
     """Step 3 of F12: the forward convolution of u (edges replicated) plus the sky, and the (damped) ratio against the data."""
     data = _image_f32(data)
-    u = _deconv_plane(u, 'u', data)
+    u = _plane_like(u, 'u', data)
     p, R = psf_stamp(psf)
-    out = _deconv_out(out, data, u)
+    out = _out_f32(out, data, u)
     check(_lib.load().apgpu_deconv_ratio_f32(_ptr(u), _ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(sky), float(gain),
                                              float(readnoise), float(damp), _ptr(out), _stream()))
     return out
@@ -2235,9 +2234,9 @@ def deconv_ratio(u, data, psf, sky, gain=1.0, readnoise=0.0, damp=0.0, out=None)
 def deconv_update(u, ratio, inv, psf, out=None):
     """Step 4 of F12: u' = (u q) inv where inv != 0, else u, with q the back-projection (correlation) of the ratio plane."""
     u = _image_f32(u, 'u')
-    ratio, inv = _deconv_plane(ratio, 'ratio', u), _deconv_plane(inv, 'inv', u)
+    ratio, inv = _plane_like(ratio, 'ratio', u), _plane_like(inv, 'inv', u)
     p, R = psf_stamp(psf)
-    out = _deconv_out(out, u, ratio)
+    out = _out_f32(out, u, ratio)
     check(_lib.load().apgpu_deconv_update_f32(_ptr(u), _ptr(ratio), _ptr(inv), u.shape[0], u.shape[1], _psf_arg(p), R, _ptr(out), _stream()))
     return out
 
@@ -2265,7 +2264,7 @@ def richardson_lucy(data, psf, sky, niter=30, damp=0.0, gain=1.0, readnoise=0.0,
         raise ValueError('niter must be >= 0, got %d' % niter)
     plane, level = None, None
     if start is not None and np.ndim(start) != 0:
-        plane = _deconv_plane(start, 'start', data)
+        plane = _plane_like(start, 'start', data)
     else:
         if start is None:
             ok = torch.isfinite(data)
@@ -2275,15 +2274,9 @@ def richardson_lucy(data, psf, sky, niter=30, damp=0.0, gain=1.0, readnoise=0.0,
         level = float(np.float32(start))
         if not (level > 0.0 and math.isfinite(level)):
             raise ValueError('the start level must be finite and > 0, got %r' % (start,))
-    out = _deconv_out(out, data, data, *(() if plane is None else (plane,)))
+    out = _out_f32(out, data, data, *(() if plane is None else (plane,)))
     lib = _lib.load()
-    need = lib.apgpu_deconv_ws_bytes(data.shape[0], data.shape[1])
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=data.device)
-    else:
-        _need_cuda(ws)
-        if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
-            raise ValueError('ws must be a contiguous, 16-byte aligned uint8 device tensor of at least %d bytes (ops.deconv_workspace)' % need)
+    ws = _workspace(ws, lib.apgpu_deconv_ws_bytes(data.shape[0], data.shape[1]), data.device, 'deconv_workspace')
     check(lib.apgpu_richardson_lucy_f32(_ptr(data), data.shape[0], data.shape[1], _psf_arg(p), R, float(sky), float(gain), float(readnoise),
                                         float(damp), niter, 0.0 if level is None else level, _ptr(plane), float(min_weight), _ptr(out),
                                         _ptr(ws), ws.numel(), _stream()))
@@ -2342,16 +2335,6 @@ def starlet_workspace(shape, device):
     return torch.empty(_lib.load().apgpu_starlet_ws_bytes(int(shape[0]), int(shape[1])), dtype=torch.uint8, device=device)
 
 
-def _starlet_ws(ws, data):
-    need = _lib.load().apgpu_starlet_ws_bytes(data.shape[0], data.shape[1])
-    if ws is None:
-        return torch.empty(need, dtype=torch.uint8, device=data.device)
-    _need_cuda(ws)
-    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.data_ptr() % 16:
-        raise ValueError('ws must be a contiguous, 16-byte aligned uint8 device tensor of at least %d bytes (ops.starlet_workspace)' % need)
-    return ws
-
-
 def starlet_step(c, spacing, out=None, plane=None, acc=None, threshold=0.0, gain=1.0, g_res=1.0, mode='hard', first=True, last=False,
                  form='auto'):
     """One launch of F13: c_j -> c_{j+1} at `spacing` = 2^j (1 .. 32) by normalised convolution with the B3 taps, NaN / inf pixels
@@ -2368,9 +2351,7 @@ def starlet_step(c, spacing, out=None, plane=None, acc=None, threshold=0.0, gain
         out = None
     for t in (out, plane, acc):
         if t is not None:
-            _need_cuda(t)
-            if t.dtype != torch.float32 or tuple(t.shape) != tuple(c.shape) or not t.is_contiguous():
-                raise ValueError('out, plane and acc must be contiguous float32 device tensors of the image shape')
+            _out_f32(t, c, name='out, plane and acc each')
     flags = (_lib.STARLET_FIRST if first else 0) | (_lib.STARLET_LAST if last else 0)
     check(_lib.load().apgpu_starlet_step_f32(_ptr(c), c.shape[0], c.shape[1], int(spacing), _ptr(out), _ptr(plane), _ptr(acc),
                                              float(threshold), float(gain), float(g_res), _starlet_mode(mode), flags, _lib.STARLET_FORM[form],
@@ -2381,7 +2362,7 @@ def starlet_step(c, spacing, out=None, plane=None, acc=None, threshold=0.0, gain
 def starlet_plane1(image, out=None):
     """w_1 = c_0 - c_1 alone (one launch): the plane the image noise is measured in."""
     image = _image_f32(image, 'image')
-    out = _deconv_out(out, image, image)
+    out = _out_f32(out, image, image)
     check(_lib.load().apgpu_starlet_plane1_f32(_ptr(image), image.shape[0], image.shape[1], _ptr(out), _stream()))
     return out
 
@@ -2391,14 +2372,8 @@ def starlet_planes(image, J=4, ws=None, out=None):
     this order is the image to within rounding.  Holes (NaN / inf pixels) are NaN in every plane.  J launches."""
     image = _image_f32(image, 'image')
     J = _starlet_scales(J)
-    shape = (J + 1,) + tuple(image.shape)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=image.device)
-    else:
-        _need_cuda(out)
-        if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise ValueError('out must be a contiguous float32 device tensor of shape %s' % (shape,))
-    ws = _starlet_ws(ws, image)
+    out = _out_f32(out, image, shape=(J + 1,) + tuple(image.shape))
+    ws = _workspace(ws, _lib.load().apgpu_starlet_ws_bytes(image.shape[0], image.shape[1]), image.device, 'starlet_workspace')
     check(_lib.load().apgpu_starlet_planes_f32(_ptr(image), image.shape[0], image.shape[1], J, _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out
 
@@ -2441,8 +2416,8 @@ def multiscale(image, J=4, k=(3.0, 3.0, 2.0, 1.0), gains=1.0, g_res=1.0, mode='h
     t = np.array([np.float32(float(k[j]) * sigma * float(se[j])) for j in range(J)], np.float32)
     if not np.all(np.isfinite(t)):
         raise ValueError('the thresholds overflow float32: %s' % (t.tolist(),))
-    out = _deconv_out(out, image, image)
-    ws = _starlet_ws(ws, image)
+    out = _out_f32(out, image, image)
+    ws = _workspace(ws, _lib.load().apgpu_starlet_ws_bytes(image.shape[0], image.shape[1]), image.device, 'starlet_workspace')
     check(_lib.load().apgpu_multiscale_f32(_ptr(image), image.shape[0], image.shape[1], J, t.ctypes.data_as(C.POINTER(C.c_float)),
                                            g.ctypes.data_as(C.POINTER(C.c_float)), float(gr), m, _ptr(out), _ptr(ws), ws.numel(), _stream()))
     return out, dict(sigma=sigma, t=t, J=J, mode=mode, k=k, gains=g.astype(np.float64), g_res=float(gr))
@@ -2513,15 +2488,6 @@ def drizzle_affines(affines, scale):
     return fine
 
 
-def _drizzle_mask(m, shape, name, dev):
-    if m is None:
-        return None
-    _need_cuda(m)
-    if tuple(m.shape) != tuple(shape):
-        raise ValueError('%s must be [%s]' % (name, ','.join('NHW'[-len(shape):])))
-    return m.contiguous() if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)
-
-
 def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, mask=None, frame_masks=None, out_shape=None,
             conserve_flux=False, cfa=None):
     """Drizzle co-add (variable-pixel linear reconstruction, "turbo" footprint, gather form) of [N,H,W] float32 frames onto a grid of
@@ -2561,8 +2527,8 @@ def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, 
         g = (fs.astype(np.float64) * np.abs(A[:, 0] * A[:, 4] - A[:, 1] * A[:, 3])).astype(np.float32)
     if not np.all(np.isfinite(g)):
         raise ValueError('the flux factors overflow float32')
-    mk = _drizzle_mask(mask, (H, W), 'mask', dev)
-    fm = _drizzle_mask(frame_masks, (N, H, W), 'frame_masks', dev)
+    mk = _mask_u8(mask, (H, W), 'mask must be [H,W]')
+    fm = _mask_u8(frame_masks, (N, H, W), 'frame_masks must be [N,H,W]')
     pat, channel = None, 0
     if cfa is not None:
         pattern, channel = cfa

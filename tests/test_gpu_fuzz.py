@@ -225,6 +225,27 @@ def test_frames_cut_out_of_an_odd_sized_slab(ops, apref):
         assert np.array_equal(fixed.cpu().numpy(), rf, equal_nan=True)
 
 
+def test_mask_in_another_layout_or_dtype(ops, apref):
+    """A mask that is a transposed view (dense, not contiguous) and is not uint8 reaches the kernel in row-major order: bool, float32
+    and uint8, through the bad-pixel repair (a mask read in the wrong layout repairs other pixels)."""
+    rng = np.random.default_rng(23)
+    H, W = 37, 53
+    img = rng.normal(500, 20, (H, W)).astype(np.float32)
+    mask = (rng.random((H, W)) < 0.03).astype(np.uint8)
+    assert mask.any() and not np.array_equal(mask, mask.T.reshape(H, W))
+    rf, rs = apref.fix_badpix(img, mask, 1)
+    d = torch.from_numpy(img).cuda()
+    for dtype in (torch.bool, torch.float32, torch.uint8):
+        view = torch.from_numpy(np.ascontiguousarray(mask.T)).cuda().to(dtype).t()
+        assert tuple(view.shape) == (H, W) and not view.is_contiguous()
+        got = ops._mask_u8(view, (H, W), 'shape')
+        assert got.is_contiguous() and got.dtype == torch.uint8 and np.array_equal(got.cpu().numpy(), mask), dtype
+        fixed, st = ops.fix_badpix(d, view, 1)
+        assert np.array_equal(fixed.cpu().numpy(), rf, equal_nan=True), dtype
+    with pytest.raises(RuntimeError, match='does not match'):
+        ops.fix_badpix(d, torch.zeros((W, H), dtype=torch.bool, device='cuda'), 1)
+
+
 def wide_case(ops, apref, seed):
     """One random stack through stack_sigclip / stack_median against the oracle over the WIDE option space: 1 .. 512 frames,
     sigma down to 0.5, clipping to convergence (the survivors can collapse to a few identical values, or vanish), NaN fractions up

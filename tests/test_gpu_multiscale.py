@@ -267,6 +267,40 @@ def test_errors():
     assert rc == _lib.E_INVAL
 
 
+def test_unaligned_base_width_multiple_of_4():
+    """A plane whose rows are a multiple of four floats but whose first pixel is not 16-byte aligned: the one branch of the shared
+    staging (csrc/plane_tile.h) and of the `wide` predicate that a fresh allocation never takes.  The blur (csrc/continuum.hip), the
+    tile form and the direct form give the bits of the model and of the aligned copy."""
+    import torch
+    from astrophotography_amd import ops
+    from tests import continuum_model as cm
+    H, W = TH + 1, 2 * TW + 4
+    img = _image(np.random.default_rng(21), H, W, 'isolated')
+    assert not np.isfinite(img).all() and np.isfinite(img).any()
+    buf = torch.empty(H * W + 1, dtype=torch.float32, device='cuda')
+    buf[1:].copy_(_dev(img).reshape(-1))
+    shifted, aligned = buf[1:].view(H, W), _dev(img)
+    assert shifted.data_ptr() % 16 != 0 and aligned.data_ptr() % 16 == 0 and shifted.is_contiguous() and W % 4 == 0
+    for R in (2, 32):
+        taps = cm.gauss_taps(R / 4.0, R)
+        want = cm.gauss_blur(img, taps, 0.5)
+        for d, tag in ((shifted, 'unaligned'), (aligned, 'aligned')):
+            _same_bits(ops.gauss_blur(d, taps, 0.5).cpu().numpy(), want, 'blur R %d %s' % (R, tag))
+    prev = np.random.default_rng(22).normal(0.0, 50.0, img.shape).astype(F)
+    for s, form in ((1, 'tile'), (8, 'tile'), (1, 'direct')):
+        cn = mm.step(img, s)
+        with np.errstate(invalid='ignore'):
+            w = np.where(np.isfinite(img), img - cn, F(np.nan)).astype(F)
+            want_acc = np.where(np.isfinite(img), prev + F(2.5) * mm.treat((img - cn).astype(F), F(30.0), 'hard'), F(np.nan)).astype(F)
+        for d, tag in ((shifted, 'unaligned'), (aligned, 'aligned')):
+            plane, acc = torch.empty_like(aligned), _dev(prev)
+            c = ops.starlet_step(d, s, plane=plane, acc=acc, threshold=30.0, gain=2.5, first=False, form=form)
+            what = 'starlet s %d %s %s' % (s, form, tag)
+            _same_bits(c.cpu().numpy(), cn, what + ' c')
+            _same_bits(plane.cpu().numpy(), w, what + ' plane')
+            _same_bits(acc.cpu().numpy(), want_acc, what + ' acc')
+
+
 # ---- end to end --------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def scene():
@@ -329,3 +363,26 @@ def test_files_and_script(scene, tmp_path):
     fitsio.write(allnan, np.full((20, 30), np.nan, F))
     with pytest.raises(RuntimeError, match='sigma'):
         script.main([allnan, out2, '-l', 'ERROR'])
+
+
+def test_uint16_file_is_widened_exactly(tmp_path):
+    """A uint16 FITS (BZERO 32768) through the file shell: the pixels reach the kernels as their exact float32 values (0, 32767, 32768
+    and 65535 are the ones a signed reading gets wrong), and the float32 output carries no BZERO / BSCALE."""
+    import astrophotography_amd as ap
+    from astrophotography_amd import fitsio
+    from astrophotography_amd.core import _common
+    raw = np.array([[0, 32767, 32768, 65535], [65535, 0, 1, 32769], [32768, 32767, 65534, 2], [1, 65535, 0, 32768]], np.uint16)
+    src, out = str(tmp_path / 'raw.fits'), str(tmp_path / 'out.fits')
+    fitsio.write(src, raw)
+    _, h0 = fitsio.read(src)
+    assert h0['BITPIX'] == 16 and h0['BZERO'] == 32768
+    log = _common.make_logger('ApMultiscale', 'ERROR')
+    got, _ = _common.read_image_f32(log, src)
+    assert got.dtype.is_floating_point and got.is_cuda and got.is_contiguous()
+    _same_bits(got.cpu().numpy(), raw.astype(F), 'read_image_f32')
+    rep = ap.ApMultiscale('ERROR', scales=2, k=0.0, gains=1.0, residual_gain=1.0).process_file(src, out, sigma=1.0)
+    assert rep['J'] == 2
+    data, h = fitsio.read(out)
+    assert 'BZERO' not in h and 'BSCALE' not in h and h['BITPIX'] == -32
+    want, _ = mm.multiscale(raw.astype(F), 2, (0.0, 0.0), (1.0, 1.0), 1.0, 'hard', sigma=1.0)
+    _same_bits(np.asarray(data, F), want, 'uint16 file against the model of the widened input')
