@@ -135,11 +135,11 @@ def _dtype_tag(t, what, allow_u16=False):
 def flat_normalize(flat):
     """A1 ApCalibrate._generate_flat (ApCalibrate.py:166-190): returns (nflat, norm[1] device tensor), both in the
     flat's own dtype - float32, or float64 for a float64 master (the reference keeps float FITS data as stored,
-    ApCalibrate.py:301-305)."""
+    ApCalibrate.py:301-305).  A flat that does not start on a 16-byte boundary is copied once (the kernels take aligned planes)."""
     _need_cuda(flat)
     lib = _lib.load()
     if flat.dtype == torch.float64:
-        flat = flat.contiguous()
+        flat = _aligned16(flat)                             # both forms take a 16-byte aligned plane
         n = flat.numel()
         ws_bytes = lib.apgpu_flat_normalize_f64_ws_bytes(n)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=flat.device)
@@ -147,7 +147,7 @@ def flat_normalize(flat):
         norm = torch.empty(1, dtype=torch.float64, device=flat.device)
         check(lib.apgpu_flat_normalize_f64(_ptr(flat), _ptr(nflat), _ptr(norm), n, _ptr(ws), ws_bytes, _stream()))
         return nflat, norm
-    flat = _f32c(flat, 'flat')
+    flat = _aligned16(_f32c(flat, 'flat'))
     n = flat.numel()
     ws_bytes = lib.apgpu_flat_normalize_ws_bytes(n)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=flat.device)
@@ -158,17 +158,22 @@ def flat_normalize(flat):
 
 
 def calibrate(raw, bias, dark, nflat, exp_ratio, pedestal=None, dark_still_biased=False, out=None):
-    """A2 ApCalibrate.calibrate arithmetic (ApCalibrate.py:439-464) on raw[H,W] or a slab raw[N,H,W]."""
+    """A2 ApCalibrate.calibrate arithmetic (ApCalibrate.py:439-464) on raw[H,W] or a slab raw[N,H,W].
+
+    The float32 kernel takes 16-byte aligned planes: raw, bias, dark and nflat are copied once when they are not (a frame cut out of
+    a slab with an odd pixel count); the results are the same bits.  out, when given, must itself start on a 16-byte boundary
+    (every torch allocation does): the library refuses any other."""
     _need_cuda(raw, bias, dark, nflat)
     lib = _lib.load()
     raw = raw.contiguous()
     if any(t is not None and t.dtype == torch.float64 for t in (raw, bias, dark, nflat)):
         return _calibrate_mixed(raw, bias, dark, nflat, exp_ratio, pedestal, dark_still_biased, out)
     dt = _raw_dtype(raw)
+    raw = _aligned16(raw)                                   # apgpu_calibrate takes 16-byte aligned planes
     single = raw.dim() == 2
     N = 1 if single else raw.shape[0]
     P = raw[0].numel() if not single else raw.numel()
-    bias, dark, nflat = _f32c(bias, 'bias'), _f32c(dark, 'dark'), _f32c(nflat, 'nflat')
+    bias, dark, nflat = (None if t is None else _aligned16(t) for t in (_f32c(bias, 'bias'), _f32c(dark, 'dark'), _f32c(nflat, 'nflat')))
     for nm, t in (('bias', bias), ('dark', dark), ('nflat', nflat)):
         if t is not None and t.numel() != P:
             raise RuntimeError('%s has %d pixels, frames have %d' % (nm, t.numel(), P))
