@@ -147,12 +147,13 @@ __global__ __launch_bounds__(COLS ? kColBlock : kMedBlock) void axis_median_kern
         if (s.n == 0) {
             med = (T)__builtin_nan("");
         } else {
+            // both of numpy's paths sum the middle element(s) from +0: a median of -0.0 is +0.0
             const T hi = K::from(s.prefix);
             if (s.n & 1) {
-                med = len < kMaPathLen ? (T)(hi + hi) / (T)2 : hi;         // np.ma.median sums the duplicated middle value
+                med = len < kMaPathLen ? (T)((T)0 + hi + hi) / (T)2 : (T)0 + hi;   // np.ma.median sums the duplicated middle value
             } else {
                 const T lo = K::from(s.need_below ? (U)below_sh[t] : s.below);
-                med = (T)(lo + hi) / (T)2;
+                med = (T)((T)0 + lo + hi) / (T)2;
             }
         }
         out[frame * nlines + line0 + t] = med;

@@ -240,13 +240,13 @@ __device__ unsigned block_select(const float *buf, int n, int k, int *cnt)
     return ans;
 }
 
-// np.median of buf[0 .. n), n >= 1, no NaN
+// np.median of buf[0 .. n), n >= 1, no NaN: np.mean of the middle element(s), whose sum starts from +0 (a median of -0.0 is +0.0)
 __device__ float block_median(const float *buf, int n, int *cnt)
 {
     const float hi = Key::from(block_select(buf, n, n / 2, cnt));
-    if (n & 1) return hi;
+    if (n & 1) return 0.0f + hi;
     const float lo = Key::from(block_select(buf, n, n / 2 - 1, cnt));
-    return (lo + hi) / 2.0f;
+    return (0.0f + lo + hi) / 2.0f;
 }
 
 __global__ __launch_bounds__(kPhotBlock) void aperture_phot_kernel(const float *__restrict__ data, long long H, long long W,

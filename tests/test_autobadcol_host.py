@@ -122,3 +122,23 @@ def test_class_is_exported_lazily():
         obj.process(np.zeros(5, np.float32))
     with pytest.raises(ValueError):
         obj.process_slab(np.zeros((4, 5), np.float32))
+
+
+def test_np_clip_stats_reproduces_astropy_g16():
+    """tests/util.np_clip_stats, the numpy restatement the GPU tests of the sliding statistics compare with, against astropy's
+    own sigma_clipped_stats on the float32 vectors of golden group G16 (12 .. 1252 values, stars and non-finite values among
+    them): mean, median and std of its survivors equal astropy's, bit for bit."""
+    import json
+    import warnings
+    from tests.util import assert_biteq, load_golden, np_clip_stats
+    g = load_golden('g16_annulus.npz')
+    meta = json.loads(str(g['_meta']))
+    assert len(meta) >= 30
+    for m in meta:
+        v = g['c%d_values' % m['case']]
+        assert v.dtype == np.float32 and m['stat_dtype'] == 'float32'
+        x = np_clip_stats(v)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore', RuntimeWarning)
+            got = np.array([np.mean(x), np.median(x), np.std(x)], np.float64)
+        assert_biteq(got, np.asarray(g['c%d_stats' % m['case']], np.float64), m['name'])

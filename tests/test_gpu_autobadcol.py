@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import GOLDEN, assert_biteq, load_golden
+from tests.util import GOLDEN, assert_biteq, load_golden, np_clip_stats as _np_clip_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -85,22 +85,6 @@ def test_script_stdout_matches_reference(run):
     with contextlib.redirect_stdout(buf):
         assert s.main([path, '-l', 'CRITICAL'] + rec['argv']) == 0
     assert buf.getvalue() == rec['stdout'].replace(META['placeholder'], path)
-
-
-def _np_clip_stats(x, sigma=3.0, maxiters=5):
-    """astropy's noaxis sigma_clipped_stats restated with the numpy functions it calls (host reference for samples)."""
-    x = x[np.isfinite(x)]
-    for _ in range(maxiters):
-        if x.size == 0:
-            break
-        med = np.nanmedian(x)
-        sd = np.nanstd(x)
-        y = x[(x >= med - sd * sigma) & (x <= med + sd * sigma)]
-        changed = y.size != x.size
-        x = y
-        if not changed:
-            break
-    return x
 
 
 def _structured(rng, H, W, badcols, badrows, dtype=np.float32):

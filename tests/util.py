@@ -55,6 +55,27 @@ def assert_biteq(a, b, what=''):
     assert ok.all(), '%s: %d of %d differ, first at %s' % (what, (~ok).sum(), ok.size, np.argwhere(~ok)[:3].tolist())
 
 
+def np_clip_stats(x, sigma=3.0, maxiters=5):
+    """astropy's noaxis sigma_clipped_stats restated with the numpy functions it calls (host reference for samples)."""
+    x = x[np.isfinite(x)]
+    for _ in range(maxiters):
+        if x.size == 0:
+            break
+        med = np.nanmedian(x)
+        sd = np.nanstd(x)
+        # SigmaClip._compute_bounds: scalar of the dtype * python float is float64 under the reference's numpy; the array
+        # comparison demotes the bound to the dtype (csrc/autobadcol.hip, findstars_model.annulus_clip)
+        with np.errstate(all='ignore'):
+            lo = x.dtype.type(np.float64(med) - np.float64(sd) * sigma)
+            hi = x.dtype.type(np.float64(med) + np.float64(sd) * sigma)
+        y = x[(x >= lo) & (x <= hi)]
+        changed = y.size != x.size
+        x = y
+        if not changed:
+            break
+    return x
+
+
 def synth_cube(rng, N, shape, nan_frac=0.0, dtype=np.float32):
     """Frames with Gaussian noise, cosmic-ray-like positive outliers and a few low outliers."""
     cube = rng.normal(500, 20, (N,) + tuple(shape))
