@@ -30,6 +30,7 @@ STARLET_MODE = {'hard': 0, 'soft': 1}                   # APGPU_STARLET_HARD, AP
 STARLET_FIRST, STARLET_LAST = 1, 2                      # APGPU_STARLET_FIRST, APGPU_STARLET_LAST
 STARLET_FORM = {'auto': 0, 'tile': 1, 'direct': 2}      # APGPU_STARLET_FORM_*
 DRIZZLE_TILE_H, DRIZZLE_TILE_W = 4, 64                  # APGPU_DRIZZLE_TILE_H, APGPU_DRIZZLE_TILE_W
+DEMOSAIC_RCD_TILE_H, DEMOSAIC_RCD_TILE_W, DEMOSAIC_RCD_HALO = 32, 64, 10     # APGPU_DEMOSAIC_RCD_TILE_H, _TILE_W, _HALO
 
 
 class ApGpuError(RuntimeError):

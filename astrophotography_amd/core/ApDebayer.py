@@ -2,14 +2,15 @@
 balance from the image :291-366, rgb() :401-486, grey() :488-587, split() :111-128).
 
 The reference leaves the interpolation to LibRaw (rawpy.postprocess), which is not in its tree; this stage defines its own
-(restated in tests/demosaic_model.py): bilinear, Malvar-He-Cutler 2004 or one pixel per 2 x 2 cell, every sample
-black-subtracted and scaled by its colour's white-balance gain once, in one kernel launch (csrc/demosaic.hip).
+(restated in tests/demosaic_model.py and tests/demosaic_rcd_model.py): bilinear, Malvar-He-Cutler 2004, one pixel per
+2 x 2 cell, or the edge-directed RCD (modelled on RCD 2.x), every sample black-subtracted and scaled by its colour's white-balance
+gain once, in one kernel launch (csrc/demosaic.hip).
 
   device  the per-colour sums of the white balance, the demosaic, FITS decode and encode
   host    the four gains from the eight numbers, headers
 
 Out of scope: decoding camera RAW files and their EXIF data, the camera's own and the daylight white balance (LibRaw metadata),
---renormalize (ApComposite's levels cover the stretch), adaptive demosaics such as AHD.
+--renormalize (ApComposite's levels cover the stretch), other adaptive demosaics such as AHD, RCD's refinement passes.
 """
 import ast
 import os
@@ -21,7 +22,7 @@ from . import _common
 
 ARRANGEMENTS = {'RGGB': (0, 1, 3, 2), 'BGGR': (2, 1, 3, 0), 'GRBG': (1, 0, 2, 3), 'GBRG': (1, 2, 0, 3)}
 WB_METHODS = ['daylight', 'camera', 'auto', 'region', 'user']          # RawConv.py:375
-METHODS = ('bilinear', 'mhc', 'superpixel')
+METHODS = ('bilinear', 'mhc', 'superpixel', 'rcd')
 LUMINANCE_METHODS = ('linear', 'direct')
 WB_KEYWORDS = ('WBRED', 'WBGREEN1', 'WBBLUE', 'WBGREEN2')
 
@@ -99,15 +100,16 @@ class ApDebayer:
 
     def rgb(self, mosaic, pattern, method='mhc', wb_method='auto', subtract_black=True, black=None, as_uint16=False):
         """[3, h, w] (or [N, 3, h, w]) float32 planes of mosaic [H, W] / [N, H, W]; as_uint16: clipped to 0 .. 65535 and truncated
-        (RawConv.rgb's np.clip + astype).  A slab takes the white balance of its first frame.  subtract_black False: the black
-        levels stay in the data (--keepblack)."""
+        (RawConv.rgb's np.clip + astype).  method: 'bilinear', 'mhc', 'superpixel' (h = H / 2) or 'rcd' (edge-directed: no zippers
+        along edges, no coloured rims on stars; nothing is clamped, so a colour may undershoot below 0 beside a bright edge).  A slab
+        takes the white balance of its first frame.  subtract_black False: the black levels stay in the data (--keepblack)."""
         from .. import ops
         pattern, black = self._prepare(mosaic, pattern, method, wb_method, subtract_black, black)
         return ops.bayer_demosaic(mosaic, pattern, black, self.gains, method, 'rgb_u16' if as_uint16 else 'rgb')
 
     def grey(self, mosaic, pattern, method='mhc', wb_method='auto', subtract_black=True, black=None, luminance_method='linear'):
         """The luminance [h, w] float32: 'linear' the CCIR 601 weights on the demosaiced colours (RawConv.py:549-556), 'direct' every
-        sample times its white-balance gain, no interpolation (:533-547)."""
+        sample times its white-balance gain, no interpolation (:533-547; method is ignored).  method: as in rgb()."""
         from .. import ops
         if luminance_method not in LUMINANCE_METHODS:
             raise ValueError(f'Unexpected luminance calculate method supplied to ApDebayer.grey: {luminance_method}. '
@@ -134,7 +136,8 @@ class ApDebayer:
         """Reads one FITS mosaic and writes out_root_r.fits, out_root_g.fits and out_root_b.fits (float32), or, with grey = a file
         name, the luminance alone.  pattern: RGGB, BGGR, GRBG or GBRG (or four colour indices), else the BAYERPAT keyword shifted
         by XBAYROFF / YBAYROFF; it applies to the array rows in file order.  The input header is passed through with HISTORY lines
-        and DEBAYER, WBRED, WBGREEN1, WBBLUE, WBGREEN2.  Returns the list of files written."""
+        and DEBAYER (BILINEAR, MHC, SUPERPIXEL, RCD or DIRECT), WBRED, WBGREEN1, WBBLUE, WBGREEN2.  Returns the list of files
+        written."""
         import torch
         _common.check_file_exists(self._logger, infile)
         data, hdr = fitsio.read_device(str(infile))

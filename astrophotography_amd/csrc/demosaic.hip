@@ -14,7 +14,23 @@
 //              at G: colour of the row    = (((10 C + 8 we) + ns2) - 2 (d4 + we2)) / 16
 //                    colour of the column = (((10 C + 8 ns) + we2) - 2 (d4 + ns2)) / 16
 //   SUPERPIXEL one pixel per 2 x 2 cell: R = s_R, G = (s_G1 + s_G2) 0.5, B = s_B
-//   outputs    RGB_F32; RGB_U16 = (uint16)(v > 0 ? (v < 65535 ? v : 65535) : 0); GREY_F32 = (0.299f R + 0.587f G) + 0.114f B;
+//   RCD        ratio-corrected, edge-directed (modelled on RCD 2.x, PARITY UNPINNED; tests/demosaic_rcd_model.py).  IEEE division;
+//              eps = 2^-10, epssq = 2^-20; s folded to all positions, every plane outside the image computed on that extension.
+//              t(n) the plane n steps along the direction; pair(g1, e1, g2, e2) = (g2 e1 + g1 e2) / (g1 + g2)
+//              1 all sites, along V and H: h = (((t(-3) + t(3)) - (t(-1) + t(1))) - 3 (t(-2) + t(2))) + 6 s, q = h h,
+//                stat = (q(-1) + q(+1)) + q(0), stat < epssq -> epssq (NaN stays); VH = V / (V + H);
+//                vd = |0.5 - VH| < |0.5 - vn| ? vn : VH, vn = 0.25 d4(VH)
+//              2 R/B sites: lpf = (s + 0.5 (ns + we)) + 0.25 d4(s)
+//              3 G at R/B sites, towards N, S, W, E: grad = (((eps + |t(1) - t(-1)|) + |s - t(2)|) + |t(1) - t(3)|) + |t(2) - t(4)|,
+//                est = t(1) (1 + (lpf - lpf(2)) / ((eps + lpf) + lpf(2))); V_est = pair(gN, eN, gS, eS), H_est = pair(gW, eW, gE, eE);
+//                G = vd H_est + (1 - vd) V_est
+//              4 R/B sites: P, Q the stat of step 1 along NW-SE, NE-SW; D = (P - Q) / (P + Q)   (= 2 PQ - 1: exactly odd in P, Q)
+//              5 other of R/B at R/B sites: dd = |D| < |dn| ? dn : D, dn = 0.25 d4(D); towards each diagonal d:
+//                grad = ((eps + |s(d) - s(-d)|) + |s(d) - s(3d)|) + |G - G(2d)|, est = s(d) - G(d);
+//                P_est = pair(gNW, eNW, gSE, eSE), Q_est = pair(gNE, eNE, gSW, eSW); O = G + ((0.5 (1 - dd)) P_est + (0.5 (1 + dd)) Q_est)
+//              6 R, B at G sites, X the colour at the R/B sites (s where native, else O), towards N, S, W, E:
+//                grad = ((eps + |G - G(2)|) + |X(1) - X(-1)|) + |X(1) - X(3)|, est = X(1) - G(1); value = G + ((1 - vd) V_est + vd H_est)
+//   outputs    RGB_F32; RGB_U16 =(uint16)(v > 0 ? (v < 65535 ? v : 65535) : 0); GREY_F32 = (0.299f R + 0.587f G) + 0.114f B;
 //              DIRECT_F32 = s
 //
 // The stencil kernel: a workgroup of 256 lanes owns a tile of 16 rows x 256 columns.  It stages the scaled samples of the tile and
@@ -222,6 +238,258 @@ __global__ __launch_bounds__(kBlock) void demosaic_kernel(const InT *__restrict_
     if (rows > 3) row_out<METHOD, G0, 3, OUTPUT>(w, a.rpos, dst + 3 * (size_t)W, plane, n);
 }
 
+// ---- RCD --------------------------------------------------------------------------------------------------------------------
+// Margins of the planes around the tile, in pixels: a plane of margin m covers rows -m .. kRcdTileH + m - 1 and columns
+// -m .. kRcdTileW + m - 1 of the tile.  Each follows from what reads it: the output reads O at distance 3 and VH at 1; O reads D at
+// 1 and G at 2 (diagonally); G reads VH at 1, lpf at 2 and s at 4; VH and D read s at 4; lpf reads s at 1.
+constexpr int kRcdTileH = APGPU_DEMOSAIC_RCD_TILE_H, kRcdTileW = APGPU_DEMOSAIC_RCD_TILE_W;
+constexpr int kRcdMO = 3, kRcdMD = kRcdMO + 1, kRcdMG = kRcdMO + 2, kRcdMVH = kRcdMG + 1, kRcdMLpf = kRcdMG + 2, kRcdMS = kRcdMVH + 4;
+static_assert(kRcdMS == APGPU_DEMOSAIC_RCD_HALO && kRcdMS >= kRcdMD + 4 && kRcdMS >= kRcdMLpf + 1, "the halo is the reach of the samples");
+static_assert(kRcdTileH * kRcdTileW == 8 * kBlock && kRcdTileW % 4 == 0 && kRcdTileH % 2 == 0 && kRcdMS % 2 == 0,
+              "a lane owns a 2 x 4 block of the tile; the tile origin and the halo are even");
+constexpr int kRcdSW = kRcdTileW + 2 * kRcdMS, kRcdSH = kRcdTileH + 2 * kRcdMS;              // 84 x 52: the samples
+constexpr int kRcdVW = kRcdTileW + 2 * kRcdMVH, kRcdVH = kRcdTileH + 2 * kRcdMVH;            // 76 x 44: VH, at all sites
+// lpf, G, D and O live on the R/B sites alone: one column parity per row, kept at ((x + kRcdHalfX) >> 1)
+constexpr int kRcdHalfX = 8, kRcdHalfW = (kRcdTileW + 2 * kRcdHalfX) / 2;                   // 40
+static_assert(kRcdHalfX % 2 == 0 && kRcdHalfX >= kRcdMLpf, "the half planes start on an even column left of every margin");
+constexpr int kRcdLdsFloats = kRcdSW * kRcdSH + kRcdVW * kRcdVH + kRcdHalfW * ((kRcdTileH + 2 * kRcdMLpf) + (kRcdTileH + 2 * kRcdMG) + (kRcdTileH + 2 * kRcdMO));
+static_assert(kRcdLdsFloats * 4 <= 64 * 1024, "the planes fit a static LDS allocation");
+constexpr float kRcdEps = 0x1p-10f, kRcdEpsSq = 0x1p-20f;
+
+// The folded reflection at any distance: period 2 (n - 1), n >= 2.
+__device__ __forceinline__ long long fold(long long i, long long n)
+{
+    if (i >= 0 && i < n) return i;
+    const long long period = 2 * (n - 1);
+    long long m = i % period;
+    m = m < 0 ? m + period : m;
+    return m < n ? m : period - m;
+}
+
+// Step 1 on nine samples along one direction (a[4] the site): h at the site and its two neighbours, squared and summed.
+__device__ __forceinline__ float rcd_h(const float (&a)[9], int i)
+{
+    return (((a[i - 3] + a[i + 3]) - (a[i - 1] + a[i + 1])) - 3.0f * (a[i - 2] + a[i + 2])) + 6.0f * a[i];
+}
+
+__device__ __forceinline__ float rcd_stat(const float (&a)[9])
+{
+    const float hm = rcd_h(a, 3), h0 = rcd_h(a, 4), hp = rcd_h(a, 5);
+    const float stat = (hm * hm + hp * hp) + h0 * h0;
+    return stat < kRcdEpsSq ? kRcdEpsSq : stat;            // a NaN stays
+}
+
+__device__ __forceinline__ float rcd_d4(float nw, float ne, float sw, float se) { return (nw + ne) + (sw + se); }
+
+// The value itself, or the mean of its four diagonal neighbours where that is farther from 0.5.
+__device__ __forceinline__ float rcd_disc(float centre, float near)
+{
+    return fabsf(0.5f - centre) < fabsf(0.5f - near) ? near : centre;
+}
+
+// The estimates of two opposite directions, each weighted by the other's gradient.
+__device__ __forceinline__ float rcd_pair(float g1, float e1, float g2, float e2) { return (g2 * e1 + g1 * e2) / (g1 + g2); }
+
+// Step 3 towards one side of the nine samples a (SGN -1: towards a[0]): the gradient and the ratio-corrected estimate.
+template <int SGN>
+__device__ __forceinline__ void rcd_green_towards(const float (&a)[9], float lpf, float lpf2, float &grad, float &est)
+{
+    const float c = a[4], t1 = a[4 + SGN], tm1 = a[4 - SGN], t2 = a[4 + 2 * SGN], t3 = a[4 + 3 * SGN], t4 = a[4 + 4 * SGN];
+    grad = (((kRcdEps + fabsf(t1 - tm1)) + fabsf(c - t2)) + fabsf(t1 - t3)) + fabsf(t2 - t4);
+    est = t1 * (1.0f + (lpf - lpf2) / ((kRcdEps + lpf) + lpf2));
+}
+
+// Step 6 for one colour at a green site: g the green there, dg[d] = eps + |G - G(2)|, x1[d], x3[d] the colour one and three steps
+// towards d = N, S, W, E, g1[d] the green one step that way.
+__device__ __forceinline__ float rcd_at_green(float g, float vd, const float (&dg)[4], const float (&x1)[4], const float (&x3)[4],
+                                              const float (&g1)[4])
+{
+    float grad[4], est[4];
+#pragma unroll
+    for (int d = 0; d < 4; d++) {
+        grad[d] = (dg[d] + fabsf(x1[d] - x1[d ^ 1])) + fabsf(x1[d] - x3[d]);
+        est[d] = x1[d] - g1[d];
+    }
+    const float v_est = rcd_pair(grad[0], est[0], grad[1], est[1]);
+    const float h_est = rcd_pair(grad[2], est[2], grad[3], est[3]);
+    return g + ((1.0f - vd) * v_est + vd * h_est);
+}
+
+// RCD in one launch: a workgroup of 256 lanes owns a tile of 32 rows x 64 columns and keeps every intermediate plane in LDS.  It
+// stages the scaled samples of the tile and a halo of 10 on every side, then runs the steps of the definition over regions that
+// shrink by each step's reach, a barrier between them; D takes the place of lpf, which is dead after the green step.  Last, a lane
+// produces a 2 x 4 block of the tile (all cell positions compile-time constants) and stores it like the stencil kernel does.
+// grid = (tiles across, tiles down, frames).
+template <typename InT, int OUTPUT, bool G0, typename OutT>
+__global__ __launch_bounds__(kBlock) void rcd_kernel(const InT *__restrict__ mosaic, long long H, long long W, const BayerArgs a,
+                                                    OutT *__restrict__ out)
+{
+    __shared__ float s_[kRcdSH * kRcdSW];
+    __shared__ float vh_[kRcdVH * kRcdVW];
+    __shared__ float lpf_[(kRcdTileH + 2 * kRcdMLpf) * kRcdHalfW];          // then D
+    __shared__ float g_[(kRcdTileH + 2 * kRcdMG) * kRcdHalfW];
+    __shared__ float o_[(kRcdTileH + 2 * kRcdMO) * kRcdHalfW];
+    constexpr int kPlanes = OUTPUT == APGPU_DEMOSAIC_GREY_F32 ? 1 : 3;
+    constexpr int NG = G0 ? 1 : 0;                       // an R/B site has (x + y) & 1 == NG
+    const size_t plane = (size_t)H * (size_t)W;
+    const long long tx0 = (long long)blockIdx.x * kRcdTileW, ty0 = (long long)blockIdx.y * kRcdTileH;
+    const InT *src = mosaic + (size_t)blockIdx.z * plane;
+    const int tid = threadIdx.x;
+    auto S = [&](int y, int x) -> float & { return s_[(y + kRcdMS) * kRcdSW + (x + kRcdMS)]; };
+    auto VH = [&](int y, int x) -> float & { return vh_[(y + kRcdMVH) * kRcdVW + (x + kRcdMVH)]; };
+    auto LPF = [&](int y, int x) -> float & { return lpf_[(y + kRcdMLpf) * kRcdHalfW + ((x + kRcdHalfX) >> 1)]; };
+    auto D = [&](int y, int x) -> float & { return lpf_[(y + kRcdMD) * kRcdHalfW + ((x + kRcdHalfX) >> 1)]; };
+    auto G = [&](int y, int x) -> float & { return g_[(y + kRcdMG) * kRcdHalfW + ((x + kRcdHalfX) >> 1)]; };
+    auto O = [&](int y, int x) -> float & { return o_[(y + kRcdMO) * kRcdHalfW + ((x + kRcdHalfX) >> 1)]; };
+
+    // the samples, folded at any distance from the image
+    for (int i = tid; i < kRcdSH * kRcdSW; i += kBlock) {
+        const int yi = i / kRcdSW, xi = i - yi * kRcdSW;
+        const long long gr = fold(ty0 + yi - kRcdMS, H), gc = fold(tx0 + xi - kRcdMS, W);
+        const int p = (int)(gr & 1) * 2 + (int)(gc & 1);
+        s_[i] = scaled_sample(src[(size_t)gr * (size_t)W + (size_t)gc], sel4(a.black_i, p), sel4(a.black_f, p), sel4(a.gain, p));
+    }
+    __syncthreads();
+
+    // 1: VH at all sites of its margin
+    for (int i = tid; i < kRcdVH * kRcdVW; i += kBlock) {
+        const int yi = i / kRcdVW, y = yi - kRcdMVH, x = i - yi * kRcdVW - kRcdMVH;
+        float col[9], row[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            col[k] = S(y + k - 4, x);
+            row[k] = S(y, x + k - 4);
+        }
+        const float v = rcd_stat(col), h = rcd_stat(row);
+        vh_[i] = v / (v + h);
+    }
+    // 2: lpf at the R/B sites of its margin
+    {
+        constexpr int m = kRcdMLpf, nh = (kRcdTileW + 2 * m) / 2, n = (kRcdTileH + 2 * m) * nh;
+        for (int i = tid; i < n; i += kBlock) {
+            const int yi = i / nh, y = yi - m, x = 2 * (i - yi * nh) - m + (((y - m) & 1) ^ NG);
+            const float ns = S(y - 1, x) + S(y + 1, x), we = S(y, x - 1) + S(y, x + 1);
+            LPF(y, x) = (S(y, x) + 0.5f * (ns + we)) + 0.25f * rcd_d4(S(y - 1, x - 1), S(y - 1, x + 1), S(y + 1, x - 1), S(y + 1, x + 1));
+        }
+    }
+    __syncthreads();
+
+    // 3: green at the R/B sites
+    {
+        constexpr int m = kRcdMG, nh = (kRcdTileW + 2 * m) / 2, n = (kRcdTileH + 2 * m) * nh;
+        for (int i = tid; i < n; i += kBlock) {
+            const int yi = i / nh, y = yi - m, x = 2 * (i - yi * nh) - m + (((y - m) & 1) ^ NG);
+            float col[9], row[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                col[k] = S(y + k - 4, x);
+                row[k] = S(y, x + k - 4);
+            }
+            const float vd = rcd_disc(VH(y, x), 0.25f * rcd_d4(VH(y - 1, x - 1), VH(y - 1, x + 1), VH(y + 1, x - 1), VH(y + 1, x + 1)));
+            const float lpf = LPF(y, x);
+            float gn, gs, gw, ge, en, es, ew, ee;
+            rcd_green_towards<-1>(col, lpf, LPF(y - 2, x), gn, en);
+            rcd_green_towards<1>(col, lpf, LPF(y + 2, x), gs, es);
+            rcd_green_towards<-1>(row, lpf, LPF(y, x - 2), gw, ew);
+            rcd_green_towards<1>(row, lpf, LPF(y, x + 2), ge, ee);
+            const float v_est = rcd_pair(gn, en, gs, es), h_est = rcd_pair(gw, ew, ge, ee);
+            G(y, x) = vd * h_est + (1.0f - vd) * v_est;
+        }
+    }
+    __syncthreads();
+
+    // 4: D = (P - Q) / (P + Q) at the R/B sites, over lpf
+    {
+        constexpr int m = kRcdMD, nh = (kRcdTileW + 2 * m) / 2, n = (kRcdTileH + 2 * m) * nh;
+        for (int i = tid; i < n; i += kBlock) {
+            const int yi = i / nh, y = yi - m, x = 2 * (i - yi * nh) - m + (((y - m) & 1) ^ NG);
+            float nwse[9], nesw[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                nwse[k] = S(y + k - 4, x + k - 4);
+                nesw[k] = S(y - k + 4, x + k - 4);
+            }
+            const float p = rcd_stat(nwse), q = rcd_stat(nesw);
+            D(y, x) = (p - q) / (p + q);
+        }
+    }
+    __syncthreads();
+
+    // 5: the other of R/B at the R/B sites
+    {
+        constexpr int m = kRcdMO, nh = (kRcdTileW + 2 * m) / 2, n = (kRcdTileH + 2 * m) * nh;
+        for (int i = tid; i < n; i += kBlock) {
+            const int yi = i / nh, y = yi - m, x = 2 * (i - yi * nh) - m + (((y - m) & 1) ^ NG);
+            const float g = G(y, x), dc = D(y, x);
+            const float dn = 0.25f * rcd_d4(D(y - 1, x - 1), D(y - 1, x + 1), D(y + 1, x - 1), D(y + 1, x + 1));
+            const float dd = fabsf(dc) < fabsf(dn) ? dn : dc;
+            float grad[4], est[4];                        // NW, SE, NE, SW
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                const int dy = (d == 0 || d == 2) ? -1 : 1, dx = (d == 0 || d == 3) ? -1 : 1;
+                const float t1 = S(y + dy, x + dx);
+                grad[d] = ((kRcdEps + fabsf(t1 - S(y - dy, x - dx))) + fabsf(t1 - S(y + 3 * dy, x + 3 * dx))) + fabsf(g - G(y + 2 * dy, x + 2 * dx));
+                est[d] = t1 - G(y + dy, x + dx);
+            }
+            const float p_est = rcd_pair(grad[0], est[0], grad[1], est[1]), q_est = rcd_pair(grad[2], est[2], grad[3], est[3]);
+            O(y, x) = g + ((0.5f * (1.0f - dd)) * p_est + (0.5f * (1.0f + dd)) * q_est);
+        }
+    }
+    __syncthreads();
+
+    // 6 and the output: lane t the rows 2 (t / 16), + 1 and the columns 4 (t % 16) .. + 3 of the tile
+    const int ly = 2 * (tid / (kRcdTileW / 4)), lx = 4 * (tid % (kRcdTileW / 4));
+    const long long y0 = ty0 + ly, x0 = tx0 + lx;
+    if (y0 >= H || x0 >= W) return;
+    const int n = (int)(W - x0 < 4 ? W - x0 : 4);
+    OutT *dst = out + (size_t)blockIdx.z * kPlanes * plane + (size_t)y0 * (size_t)W + (size_t)x0;
+#pragma unroll
+    for (int I = 0; I < 2; I++) {
+        if (y0 + I >= H) break;
+        float r[4], g[4], b[4];
+#pragma unroll
+        for (int J = 0; J < 4; J++) {
+            const int pos = (I & 1) * 2 + (J & 1);
+            const bool green = (((I ^ J) & 1) == 0) == G0;
+            const int y = ly + I, x = lx + J;
+            const float c = S(y, x);
+            if (green) {
+                const float vd = rcd_disc(VH(y, x), 0.25f * rcd_d4(VH(y - 1, x - 1), VH(y - 1, x + 1), VH(y + 1, x - 1), VH(y + 1, x + 1)));
+                const float dg[4] = {kRcdEps + fabsf(c - S(y - 2, x)), kRcdEps + fabsf(c - S(y + 2, x)), kRcdEps + fabsf(c - S(y, x - 2)),
+                                     kRcdEps + fabsf(c - S(y, x + 2))};
+                const float g1[4] = {G(y - 1, x), G(y + 1, x), G(y, x - 1), G(y, x + 1)};
+                // the colour of the row is native left and right, that of the column above and below; O holds the other
+                const float row1[4] = {O(y - 1, x), O(y + 1, x), S(y, x - 1), S(y, x + 1)};
+                const float row3[4] = {O(y - 3, x), O(y + 3, x), S(y, x - 3), S(y, x + 3)};
+                const float col1[4] = {S(y - 1, x), S(y + 1, x), O(y, x - 1), O(y, x + 1)};
+                const float col3[4] = {S(y - 3, x), S(y + 3, x), O(y, x - 3), O(y, x + 3)};
+                const float of_row = rcd_at_green(c, vd, dg, row1, row3, g1), of_col = rcd_at_green(c, vd, dg, col1, col3, g1);
+                const bool row_is_red = a.rpos == (pos ^ 1);
+                r[J] = row_is_red ? of_row : of_col;
+                g[J] = c;
+                b[J] = row_is_red ? of_col : of_row;
+            } else {
+                const float o = O(y, x);
+                const bool is_red = a.rpos == pos;
+                r[J] = is_red ? c : o;
+                g[J] = G(y, x);
+                b[J] = is_red ? o : c;
+            }
+        }
+        OutT *row = dst + (size_t)I * (size_t)W;
+        if (OUTPUT == APGPU_DEMOSAIC_GREY_F32) {
+            float yv[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) yv[j] = luma(r[j], g[j], b[j]);
+            store_run(row, yv, n);
+        } else {
+            store_run(row, r, n);
+            store_run(row + plane, g, n);
+            store_run(row + 2 * plane, b, n);
+        }
+    }
+}
+
 // SUPERPIXEL: a lane owns four consecutive output pixels of one output row (8 x 2 samples).  grid.y = frames.
 template <typename InT, int OUTPUT, typename OutT>
 __global__ __launch_bounds__(kBlock) void superpixel_kernel(const InT *__restrict__ mosaic, long long H, long long W, const BayerArgs a,
@@ -398,7 +666,10 @@ template <typename InT, int OUTPUT, typename OutT>
 void launch_method(int method, bool g0, dim3 tiles, dim3 lanes, hipStream_t s, const InT *in, long long H, long long W, const BayerArgs &a,
                    OutT *out)
 {
-    if (method == APGPU_DEMOSAIC_BILINEAR) launch_stencil<InT, APGPU_DEMOSAIC_BILINEAR, OUTPUT, OutT>(g0, tiles, s, in, H, W, a, out);
+    if (method == APGPU_DEMOSAIC_RCD) {
+        if (g0) hipLaunchKernelGGL((rcd_kernel<InT, OUTPUT, true, OutT>), tiles, dim3(kBlock), 0, s, in, H, W, a, out);
+        else hipLaunchKernelGGL((rcd_kernel<InT, OUTPUT, false, OutT>), tiles, dim3(kBlock), 0, s, in, H, W, a, out);
+    } else if (method == APGPU_DEMOSAIC_BILINEAR) launch_stencil<InT, APGPU_DEMOSAIC_BILINEAR, OUTPUT, OutT>(g0, tiles, s, in, H, W, a, out);
     else if (method == APGPU_DEMOSAIC_MHC) launch_stencil<InT, APGPU_DEMOSAIC_MHC, OUTPUT, OutT>(g0, tiles, s, in, H, W, a, out);
     else hipLaunchKernelGGL((superpixel_kernel<InT, OUTPUT, OutT>), lanes, dim3(kBlock), 0, s, in, H, W, a, out);
 }
@@ -430,7 +701,8 @@ extern "C" int apgpu_bayer_demosaic(const void *mosaic, int32_t dtype, int64_t n
         return fail(APGPU_EINVAL, "bayer_demosaic: %lld frames of %lld x %lld (at least 1 of 2 x 2)", (long long)n_frames, (long long)height, (long long)width);
     if (output < APGPU_DEMOSAIC_RGB_F32 || output > APGPU_DEMOSAIC_DIRECT_F32) return fail(APGPU_EINVAL, "bayer_demosaic: output %d", output);
     const bool direct = output == APGPU_DEMOSAIC_DIRECT_F32;
-    if (!direct && (method < APGPU_DEMOSAIC_BILINEAR || method > APGPU_DEMOSAIC_SUPERPIXEL)) return fail(APGPU_EINVAL, "bayer_demosaic: method %d", method);
+    const bool known = (method >= APGPU_DEMOSAIC_BILINEAR && method <= APGPU_DEMOSAIC_SUPERPIXEL) || method == APGPU_DEMOSAIC_RCD;          // 3 is no method
+    if (!direct && !known) return fail(APGPU_EINVAL, "bayer_demosaic: method %d", method);
     const bool super = !direct && method == APGPU_DEMOSAIC_SUPERPIXEL;
     if (super && ((height | width) & 1)) return fail(APGPU_EINVAL, "bayer_demosaic: SUPERPIXEL needs even height and width, got %lld x %lld", (long long)height, (long long)width);
     const size_t in_size = dtype == APGPU_U16 ? 2 : 4, out_size = output == APGPU_DEMOSAIC_RGB_U16 ? 2 : 4;
@@ -442,7 +714,9 @@ extern "C" int apgpu_bayer_demosaic(const void *mosaic, int32_t dtype, int64_t n
     const bool g0 = (a.pattern[0] & 1) != 0;
     const long long oh = super ? height / 2 : height, ow = super ? width / 2 : width;
     const long long lane_blocks = ((ow + 3) / 4 * oh + kBlock - 1) / kBlock;
-    const long long tiles_x = (width + kTileW - 1) / kTileW, tiles_y = (height + kTileH - 1) / kTileH;
+    const bool rcd = !direct && method == APGPU_DEMOSAIC_RCD;
+    const long long tile_w = rcd ? kRcdTileW : kTileW, tile_h = rcd ? kRcdTileH : kTileH;
+    const long long tiles_x = (width + tile_w - 1) / tile_w, tiles_y = (height + tile_h - 1) / tile_h;
     if (lane_blocks > 0x7fffffffLL || tiles_x > 0x7fffffffLL || tiles_y > kMaxGridZ)
         return fail(APGPU_EUNSUPPORTED, "bayer_demosaic: image of %lld x %lld is too large", (long long)height, (long long)width);
     const size_t in_frame = (size_t)height * (size_t)width * in_size;

@@ -1792,7 +1792,7 @@ def composite_rgb(planes, levels, tables, colour_sat, bits=8, flip=True, out=Non
 # ------------------------------------------------------------------------------------------------------------------
 # F10: ApDebayer - Bayer demosaic, white-balance scaling and the sums behind the white balance (csrc/demosaic.hip, DESIGN 4.3g;
 # LibRaw absent: the interpolation is this project's definition)
-DEMOSAIC_METHODS = {'bilinear': 0, 'mhc': 1, 'superpixel': 2}
+DEMOSAIC_METHODS = {'bilinear': 0, 'mhc': 1, 'superpixel': 2, 'rcd': 4}          # APGPU_DEMOSAIC_*; 3 is no method
 DEMOSAIC_OUTPUTS = {'rgb': 0, 'rgb_u16': 1, 'grey': 2, 'direct': 3}
 
 
@@ -1833,12 +1833,15 @@ def bayer_demosaic(mosaic, pattern=(0, 1, 3, 2), black=None, gain=None, method='
     """Colour planes of Bayer mosaics: mosaic [H, W] or [N, H, W], uint16 or float32; pattern as in bayer_split (a Bayer
     arrangement); black, gain: four values by colour (R, G1, B, G2) or None.  Every sample is float32(max(raw - black, 0)) gain.
 
-    method  'bilinear', 'mhc' (Malvar-He-Cutler 2004) or 'superpixel' (one pixel per 2 x 2 cell: H and W even, h = H / 2)
+    method  'bilinear', 'mhc' (Malvar-He-Cutler 2004), 'superpixel' (one pixel per 2 x 2 cell: H and W even, h = H / 2) or 'rcd'
+            (ratio-corrected and edge-directed, modelled on RCD 2.x: follows edges and keeps stars round where the linear filters
+            leave zippers and coloured rims; several times slower.  Its eps = 2^-10 is in sample units: bring a mosaic
+            normalised to 0 .. 1 to ADU scale with gain)
     output  'rgb' float32 [3, h, w]; 'rgb_u16' the same clipped to 0 .. 65535 and truncated; 'grey' float32 [h, w], the CCIR 601
             luminance of the colours; 'direct' float32 [H, W], the scaled samples themselves (method is ignored)
 
     A slab gives [N, 3, h, w] or [N, h, w].  out: a contiguous device tensor of that shape and dtype.  The arithmetic is DESIGN
-    4.3g / include/apgpu.h, restated in tests/demosaic_model.py."""
+    4.3g / include/apgpu.h, restated in tests/demosaic_model.py and, for 'rcd', tests/demosaic_rcd_model.py."""
     _need_cuda(mosaic, out)
     dt = _raw_dtype(mosaic)
     if mosaic.dim() not in (2, 3):

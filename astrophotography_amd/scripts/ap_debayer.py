@@ -12,7 +12,7 @@ import argparse
 import logging
 
 ALLOWED_WB = ['daylight', 'camera', 'auto', 'region[regspec]', 'user[userspec]']          # cli.py:170
-ALLOWED_METHODS = ['bilinear', 'mhc', 'superpixel']
+ALLOWED_METHODS = ['bilinear', 'mhc', 'superpixel', 'rcd']
 PATTERNS = ['RGGB', 'BGGR', 'GRBG', 'GBRG']
 
 
@@ -24,7 +24,9 @@ def command_line_opts(argv):
     parser.add_argument('-m', '--method', default='mhc', choices=ALLOWED_METHODS,
                         help='Method used to interpolate the Bayer sub channels. bilinear: means of the nearest like-coloured '
                              'neighbours. mhc: Malvar-He-Cutler gradient-corrected linear interpolation (5 x 5). superpixel: one '
-                             'output pixel per 2 x 2 cell, half the size, no interpolation. Default: mhc')
+                             'output pixel per 2 x 2 cell, half the size, no interpolation. rcd: ratio-corrected, edge-directed '
+                             'interpolation modelled on RCD 2.x: follows edges and keeps stars round and free of coloured rims, '
+                             'several times slower than mhc. Default: mhc')
     parser.add_argument('-w', '--whitebalance', default='auto',
                         help='Whitebalance to use when convert R, G and B channels. Allowed whitebalance methods are: %s '
                              'To calculate the whitebalance from the entire image use "auto". To calculate the whitebalance from '

@@ -665,6 +665,35 @@ int apgpu_composite_rgb(const float *planes, int64_t height, int64_t width, cons
  *       ((12 C + 4 d4) - 3 a4) 2^-4.  At G: the colour of the row = (((10 C + 8 we) + ns2) - 2 (d4 + we2)) 2^-4, the colour of
  *       the column = (((10 C + 8 ns) + we2) - 2 (d4 + ns2)) 2^-4.
  *     SUPERPIXEL  height and width even; one output pixel per cell: R = s_R, G = (s_G1 + s_G2) 0.5f, B = s_B.
+ *     RCD         ratio-corrected, edge-directed: modelled on RCD 2.x (L. Sanz Rodriguez), without its refinement passes; PARITY
+ *       UNPINNED (LibRaw and librtprocess are absent), restated in tests/demosaic_rcd_model.py.  IEEE division.  s is extended to
+ *       all integer positions by the folded reflection above; every intermediate plane outside the image is what the same
+ *       formulas give on that extended mosaic (NOT a reflection of the intermediate plane).  eps = 2^-10, epssq = 2^-20, in
+ *       sample units (powers of two: constant mosaics come back exactly); a float mosaic normalised to 0 .. 1 should be brought
+ *       to ADU scale with gain.  s >= 0 or NaN, so every denominator is >= eps.  t(n): the plane n steps along the direction in
+ *       question; d4(a) = (a(NW) + a(NE)) + (a(SW) + a(SE)); pair(g1, e1, g2, e2) = (g2 e1 + g1 e2) / (g1 + g2).
+ *       1 statistics, all sites, along V and H:  h = (((t(-3) + t(3)) - (t(-1) + t(1))) - 3 (t(-2) + t(2))) + 6 s, q = h h,
+ *         stat = (q(-1) + q(+1)) + q(0), stat < epssq gives epssq (a NaN stays);  VH = V / (V + H).
+ *         vd = |0.5 - VH| < |0.5 - vn| ? vn : VH with vn = 0.25 d4(VH).
+ *       2 low pass, R/B sites:  lpf = (s + 0.5 ((N + S) + (W + E))) + 0.25 d4(s).
+ *       3 green at R/B sites.  Towards each of N, S, W, E (t steps that way):
+ *           grad = (((eps + |t(1) - t(-1)|) + |s - t(2)|) + |t(1) - t(3)|) + |t(2) - t(4)|
+ *           est  = t(1) (1 + (lpf - lpf(2)) / ((eps + lpf) + lpf(2)))
+ *         V_est = pair(gN, eN, gS, eS), H_est = pair(gW, eW, gE, eE), G = vd H_est + (1 - vd) V_est.  At green sites G = s.
+ *       4 diagonal statistics, R/B sites: stat of step 1 along NW-SE (P) and NE-SW (Q);  D = (P - Q) / (P + Q).
+ *         (RCD's PQ = P / (P + Q) is (1 + D) / 2.  D changes its sign bit for bit when P and Q change places, which a mirrored
+ *         mosaic makes them do; 1 - P / (P + Q) and Q / (P + Q) differ in the last bit, so PQ would not give mirrored planes.)
+ *       5 the other of R/B at R/B sites:  dd = |D| < |dn| ? dn : D with dn = 0.25 d4(D).  Towards each diagonal d:
+ *           grad = ((eps + |s(d) - s(-d)|) + |s(d) - s(3d)|) + |G - G(2d)|,  est = s(d) - G(d)
+ *         P_est = pair(gNW, eNW, gSE, eSE), Q_est = pair(gNE, eNE, gSW, eSW),
+ *         O = G + ((0.5 (1 - dd)) P_est + (0.5 (1 + dd)) Q_est).
+ *       6 R and B at green sites, for each colour c: X = colour c at the R/B sites (s where native, O elsewhere), vd of step 1
+ *         at this site.  Towards each of N, S, W, E:
+ *           grad = ((eps + |G - G(2)|) + |X(1) - X(-1)|) + |X(1) - X(3)|,  est = X(1) - G(1)
+ *         V_est, H_est as in step 3;  value = G + ((1 - vd) V_est + vd H_est).
+ *       Nothing is clamped.  An output pixel depends on the samples within Chebyshev distance APGPU_DEMOSAIC_RCD_HALO (6 reads O
+ *       at 3, O reads G at 2 diagonally, G reads vn at 1, whose V reads s at 4).  One launch, no workspace: a workgroup keeps the
+ *       planes of a tile of APGPU_DEMOSAIC_RCD_TILE_H x APGPU_DEMOSAIC_RCD_TILE_W pixels and its halo in LDS.
  *     output      RGB_F32: out [n_frames][3][h][w] float32.  RGB_U16: the same as (uint16)(v > 0 ? (v < 65535 ? v : 65535) : 0),
  *       truncating, NaN gives 0 (np.clip + astype, RawConv.py:484-486).  GREY_F32: out [n_frames][h][w] = (0.299f R + 0.587f G) +
  *       0.114f B (CCIR 601, :550).  DIRECT_F32: out [n_frames][height][width] = s, the 'direct' luminance (:533-547); method is
@@ -678,6 +707,10 @@ int apgpu_composite_rgb(const float *planes, int64_t height, int64_t width, cons
 #define APGPU_DEMOSAIC_BILINEAR   0
 #define APGPU_DEMOSAIC_MHC        1
 #define APGPU_DEMOSAIC_SUPERPIXEL 2
+#define APGPU_DEMOSAIC_RCD        4   /* 3 is no method and stays APGPU_EINVAL, as version 130 has refused it all along */
+#define APGPU_DEMOSAIC_RCD_TILE_H 32
+#define APGPU_DEMOSAIC_RCD_TILE_W 64
+#define APGPU_DEMOSAIC_RCD_HALO   10
 #define APGPU_DEMOSAIC_RGB_F32    0
 #define APGPU_DEMOSAIC_RGB_U16    1
 #define APGPU_DEMOSAIC_GREY_F32   2

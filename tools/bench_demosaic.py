@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""F10 timing: the three demosaic methods x uint16 / float32 mosaics x RGB_F32 / RGB_U16 / GREY_F32 on one 4096 x 4096 frame and on
+"""F10 timing: the four demosaic methods x uint16 / float32 mosaics x RGB_F32 / RGB_U16 / GREY_F32 on one 4096 x 4096 frame and on
 a 16-frame slab of 2048 x 2048, and bayer_channel_sums.  Device time by HIP events (one warm-up call, then the median, minimum and
 maximum of --reps calls); algorithmic GB/s = (bytes of the mosaic read once + bytes written) / time, beside the 8 TB/s HBM peak and
 a device-to-device copy of 12 bytes per pixel.
 
-    python tools/bench_demosaic.py [--size 4096] [--slab 16 2048] [--reps 20]
+    python tools/bench_demosaic.py [--size 4096] [--shape 4176 6248] [--slab 16 2048] [--reps 20] [--methods mhc rcd]
 """
 import argparse
 import os
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 PEAK_GBS = 8000.0
-METHODS = ('bilinear', 'mhc', 'superpixel')
+METHODS = ('bilinear', 'mhc', 'superpixel', 'rcd')
 OUTPUTS = (('rgb', 12), ('rgb_u16', 6), ('grey', 4))        # bytes written per output pixel
 
 
@@ -35,10 +35,10 @@ def device_ms(fn, reps):
     return float(np.median(times)), float(np.min(times)), float(np.max(times))
 
 
-def make_mosaic(n, size, dtype, seed=5):
+def make_mosaic(n, shape, dtype, seed=5):
     import torch
     g = torch.Generator(device='cuda').manual_seed(seed)
-    m = (1200.0 + 300.0 * torch.randn((n, size, size), generator=g, device='cuda')).clamp_(0, 65535)
+    m = (1200.0 + 300.0 * torch.randn((n,) + tuple(shape), generator=g, device='cuda')).clamp_(0, 65535)
     if dtype == 'u16':
         return m.to(torch.int32).to(torch.int16).view(torch.uint16).contiguous()
     return m.contiguous()
@@ -53,6 +53,8 @@ def row(label, ms, nbytes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--size', type=int, default=4096)
+    ap.add_argument('--shape', type=int, nargs=2, default=None, metavar=('ROWS', 'COLUMNS'), help='one frame of this shape instead of --size squared')
+    ap.add_argument('--methods', nargs='+', default=list(METHODS), choices=METHODS)
     ap.add_argument('--slab', type=int, nargs=2, default=[16, 2048], metavar=('FRAMES', 'SIZE'))
     ap.add_argument('--reps', type=int, default=20)
     p = ap.parse_args()
@@ -60,16 +62,18 @@ def main():
     from astrophotography_amd import ops
     print('F10 demosaic; device %s; %d repetitions after one warm-up call' % (torch.cuda.get_device_name(0), p.reps))
     pattern, black, gain = (0, 1, 3, 2), [256, 256, 256, 256], [1.9, 1.0, 1.5, 1.0]
-    for n, size in ((1, p.size), tuple(p.slab)):
-        npix = n * size * size
-        print('%d frame(s) of %d x %d' % (n, size, size))
+    for n, shape in ((1, tuple(p.shape) if p.shape else (p.size, p.size)), (p.slab[0], (p.slab[1], p.slab[1]))):
+        npix = n * shape[0] * shape[1]
+        print('%d frame(s) of %d x %d' % (n, shape[0], shape[1]))
         src = torch.empty((3, npix), dtype=torch.float32, device='cuda')
         dst = torch.empty_like(src)
         row('device copy of 12 bytes per pixel (read + write)', device_ms(lambda: dst.copy_(src), p.reps), 24 * npix)
         del src, dst
         for dtype, in_bytes in (('u16', 2), ('f32', 4)):
-            m = make_mosaic(n, size, dtype)
-            for method in METHODS:
+            m = make_mosaic(n, shape, dtype)
+            for method in p.methods:
+                if method == 'superpixel' and (shape[0] % 2 or shape[1] % 2):
+                    continue
                 scale = 4 if method == 'superpixel' else 1
                 for output, out_bytes in OUTPUTS:
                     out = ops.bayer_demosaic(m, pattern, black, gain, method, output)
