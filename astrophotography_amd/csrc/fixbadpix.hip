@@ -4,8 +4,9 @@
 // is streamed once (out = data), the bad pixels of each tile are compacted into an LDS list, and each
 // one gathers its (2*deltapix+1)^2 window from the ORIGINAL image and mask (ApFixBadPixels.py:388-392),
 // so a repaired neighbour never feeds another repair, exactly as in the reference.
-//   good >= min_valid (4, ApFixBadPixels.py:45,397) -> out = np.median(good)   (float32: even count ->
-//   float32(a + b) / 2 through np.mean), else unchanged.  np.median returns NaN if a good value is NaN.
+//   good >= min_valid (4, ApFixBadPixels.py:45,397) -> out = np.median(good)   (np.mean of the middle element(s),
+//   summed from +0: odd count -> 0 + b, even count -> float32(0 + a + b) / 2; a median of -0.0 is +0.0), else
+//   unchanged.  np.median returns NaN if a good value is NaN.
 // HBM traffic: 4P + P read, 4P written; the gathers hit L2 (neighbouring rows were just streamed).
 #include "common.h"
 #include "stack_sort.h"
@@ -61,10 +62,11 @@ __device__ T repair_pixel(const T *__restrict__ data, const uint8_t *__restrict_
             if (lt <= k1 && k1 < le) m1 = x;
             if (lt <= k2 && k2 < le) m2 = x;
         }
-    if (ng & 1) return m2;
-    if constexpr (sizeof(T) == 8) return (m1 + m2) / 2.0;   // np.mean of the two middle float64 values
+    // np.mean of the middle element(s) starts its sum from +0: a median of -0.0 is +0.0
+    if (ng & 1) return (T)0 + m2;
+    if constexpr (sizeof(T) == 8) return ((T)0 + m1 + m2) / 2.0;   // np.mean of the two middle float64 values
     else {
-        const float t = m1 + m2;                    // float32: np.mean = float32 sum, then / 2
+        const float t = 0.0f + m1 + m2;             // float32: np.mean = float32 sum, then / 2
         return (float)((double)t / 2.0);
     }
 }
@@ -106,8 +108,8 @@ __device__ __forceinline__ float repair_window(const float *__restrict__ data, c
     apgpu_stack::sort_column<NP>(w);
     const float m1 = apgpu_stack::pick_at<NP>(w, (ng - 1) >> 1);
     const float m2 = apgpu_stack::pick_at<NP>(w, ng >> 1);
-    const float t = m1 + m2;
-    const float med = (ng & 1) ? m2 : (float)((double)t / 2.0);
+    const float t = 0.0f + m1 + m2;                 // np.mean sums from +0: a median of -0.0 is +0.0
+    const float med = (ng & 1) ? 0.0f + m2 : (float)((double)t / 2.0);
     return has_nan ? __builtin_nanf("") : med;      // np.median propagates NaN
 }
 

@@ -700,7 +700,7 @@ void apref_mask_add_rects(uint8_t *mask, long H, long W, const int32_t *rects, l
 /* A5  ApFixBadPixels.fix_bad_pixels (ref: core/ApFixBadPixels.py:292-445)                        */
 /*     For each pixel with mask != 0: window [r-d, r+d] x [c-d, c+d] clipped to the image, values */
 /*     and mask taken from the ORIGINAL arrays; if #good >= min_valid: new = np.median(good)      */
-/*     (float32: odd -> middle; even -> float32(a+b)/2 via np.mean) else unchanged.               */
+/*     (float32: odd -> 0 + middle; even -> float32(0+a+b)/2 via np.mean) else unchanged.         */
 /*     stats[0] = nbad, stats[1] = nfixed, stats[2] = nremaining.                                 */
 /* ------------------------------------------------------------------------------------------- */
 int apref_fix_badpix_f32(const float *data, const uint8_t *mask, long H, long W, int deltapix,
@@ -729,7 +729,10 @@ int apref_fix_badpix_f32(const float *data, const uint8_t *mask, long H, long W,
                 if (has_nan) out[r * W + c] = NAN;
                 else {
                     qsort(good, (size_t)ng, sizeof(float), cmp_float);
-                    out[r * W + c] = median_sorted_f32(good, ng);
+                    /* np.mean of the middle element(s) starts its sum from +0: a median of -0.0 is +0.0 */
+                    volatile float t = 0.0f + good[(ng - 1) / 2];
+                    if (!(ng & 1)) t = t + good[ng / 2];
+                    out[r * W + c] = (ng & 1) ? t : (float)((double)t / 2.0);
                 }
                 nfix++;
             }
@@ -772,7 +775,8 @@ int apref_fix_badpix_f64(const double *data, const uint8_t *mask, long H, long W
                 if (has_nan) out[r * W + c] = NAN;
                 else {
                     qsort(good, (size_t)ng, sizeof(double), cmp_double_nan_last);
-                    out[r * W + c] = (ng & 1) ? good[ng / 2] : (good[ng / 2 - 1] + good[ng / 2]) / 2.0;
+                    /* summed from +0, as above */
+                    out[r * W + c] = (ng & 1) ? 0.0 + good[ng / 2] : (0.0 + good[ng / 2 - 1] + good[ng / 2]) / 2.0;
                 }
                 nfix++;
             }

@@ -52,6 +52,9 @@ stack_median / stack_sigclip - csrc/stack_sort.h networks, csrc/stack_reduce.h p
     (boundary_b0), sign and zero order (boundary_b31_sign, zeros_*), inf and NaN padding.  Largest distance of an even-count
     median from the oracle over all kernels: 0 ulp (float32 and uint16; the family allows 1).
 sepmedfilt - csrc/lacosmic.hip medians of 5 / 7 / 9: same_* (ties), zeros_*, subnormal_*, boundary_b* in every window position.
+fix_badpix - csrc/fixbadpix.hip, repair_window<1 / 2 / 3> (sort + pick_at) and repair_pixel<float / double> (rank counting):
+    the same catalogue laid into repair windows, in a module of its own with its own reference (np.median through
+    tests/fixbadpix_model.py): tests/test_gpu_fixbadpix.py, which lists its branches the same way.
 
 Found and fixed with this module: axis_median_kernel and block_median returned -0.0 for a median of -0.0 (a line whose
 middle values are -0.0, no +0.0 in it) where np.nanmedian and np.median return +0.0 - numpy's mean of the middle element(s)
