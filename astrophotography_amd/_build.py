@@ -26,6 +26,8 @@ UNITS = ['common', 'elementwise', 'fixbadpix', 'sigclip_global', 'resample', 're
 STACK_GROUPS = ['h', 'o', 'g', 'j', 'f', 'n', 'e', 'i', 'd', 'm', 'c', 'l', 'b', 'k', 'a']
 STACK_DTYPES = [('f32', 'float'), ('u16', 'uint16_t')]
 STACK_CALIB = [('calib', 'true'), ('plain', 'false')]
+# ... and, behind them (so that every older kernel keeps its place in the loaded code), the units added since.
+LATE_UNITS = ['stack_reject']
 
 # -ffp-contract=off: the reference's NumPy expressions round after every operation, so no FMA
 # contraction anywhere; fused operations are written explicitly (fma()) where wanted.
@@ -51,6 +53,7 @@ def compile_units(obj_dir=OBJ):
     units += [('stack_inst_%s_%s_%s' % (tag, ctag, g), 'stack_inst',
                STACK_TU_FLAGS + ['-DAPGPU_INST_RAW=' + raw, '-DAPGPU_INST_CALIB=' + calib, '-DAPGPU_INST_GROUP=' + g])
               for g in STACK_GROUPS for tag, raw in STACK_DTYPES for ctag, calib in STACK_CALIB]
+    units += [(u, u, []) for u in LATE_UNITS]
     for name, src, flags in units:
         stem = os.path.join(obj_dir, name)
         srcp = os.path.join(CSRC, src + '.hip')

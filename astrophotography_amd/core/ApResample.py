@@ -17,18 +17,19 @@ import numpy as np
 from .. import __version__, fitsio
 from . import _common
 
-COMBINE_TYPES = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED')
+COMBINE_TYPES = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX')
 
 
 class ApResample:
     def __init__(self, loglevel='INFO', combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024, conserve_flux=True, oversampling=1,
-                 gain_keyword='EGAIN'):
+                 gain_keyword='EGAIN', nlow=1, nhigh=1):
         self._name = 'ApResample'
         self._logger = _common.make_logger(self._name, loglevel)
         combine = str(combine).upper()
         if combine not in COMBINE_TYPES:
             raise ValueError(f'Error, combine type {combine} is not one of the allowed types: {COMBINE_TYPES}')
         self.combine, self.sigma, self.maxiters, self.n_phases = combine, sigma, maxiters, n_phases
+        self.nlow, self.nhigh = int(nlow), int(nhigh)       # MINMAX: values dropped per pixel at either end
         self.conserve_flux = bool(conserve_flux)            # FSCALASTRO_TYPE VARIABLE (resample_all.sh:129)
         self.oversampling = int(oversampling)               # OVERSAMPLING (resample_all.sh:112: 4)
         self.gain_keyword = gain_keyword                    # GAIN_KEYWORD (resample_all.sh:111: EGAIN)
@@ -41,7 +42,8 @@ class ApResample:
         from .. import ops
         return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                          sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
-                         oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused)
+                         oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
+                         nlow=self.nlow, nhigh=self.nhigh)
 
     def _output_gain(self, gains, fscale, weights):
         """Effective gain of the co-add in electrons per output unit, written as GAIN when every input carries the
@@ -137,6 +139,12 @@ class ApResample:
                 del hdr[kw]
         hdr['NCOMBINE'] = (len(input_files), 'Number of frames combined')
         hdr['COMBINET'] = (self.combine, 'Co-add combine type')
+        if self.combine == 'WINSORIZED':
+            hdr['COMBSIG'] = (float(self.sigma), 'Winsorized clip threshold (sigma)')
+            hdr['COMBITR'] = (-1 if self.maxiters is None else int(self.maxiters), 'Maximum clipping rounds')
+        elif self.combine == 'MINMAX':
+            hdr['COMBNLO'] = (self.nlow, 'Lowest values dropped per pixel')
+            hdr['COMBNHI'] = (self.nhigh, 'Highest values dropped per pixel')
         hdr['RESAMPT'] = ('LANCZOS3', 'Resampling kernel')
         hdr['OVERSAMP'] = (self.oversampling, 'Sub-samples per output pixel and axis')
         gain_out = self._output_gain(gains, fscale, weights)

@@ -15,7 +15,8 @@ import numpy as np
 from .. import __version__, fitsio
 from . import _common
 
-METHODS = ('sigclip', 'median', 'mean')
+METHODS = ('sigclip', 'median', 'mean', 'winsorized', 'minmax')
+REJECT_METHODS = ('winsorized', 'minmax')         # ops.stack_reject: the rules for stacks of few frames
 
 
 def _apply_pedestals(slab, hdrs):
@@ -33,22 +34,32 @@ def _apply_pedestals(slab, hdrs):
 
 class ApStack:
     def __init__(self, loglevel='INFO', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=5, cenfunc='median',
-                 stdfunc='std'):
+                 stdfunc='std', nlow=1, nhigh=1):
         self._name = 'ApStack'
         self._logger = _common.make_logger(self._name, loglevel)
         self.sigma, self.sigma_lower, self.sigma_upper = sigma, sigma_lower, sigma_upper
         self.maxiters, self.cenfunc, self.stdfunc = maxiters, cenfunc, stdfunc
+        self.nlow, self.nhigh = nlow, nhigh
 
     def stack(self, frames, method='sigclip', calib=None, pixmask=None, outputs=('mean',)):
         """frames[N,H,W] device tensor (uint16|float32) -> dict of device tensors.
 
         method 'sigclip': clipped mean (+ 'median', 'std', 'count', 'moments' planes on request);
-        'mean': plain mean (a clip with an infinite bound, one pass); 'median': np.nanmedian along N.
+        'mean': plain mean (a clip with an infinite bound, one pass); 'median': np.nanmedian along N;
+        'winsorized': Winsorized sigma clip at sigma / sigma_lower / sigma_upper, maxiters rounds, and 'minmax': the nlow
+        lowest and nhigh highest values of a pixel dropped - the rules for 5 .. 30 frames, at most 128 (ops.stack_reject;
+        outputs 'mean', 'std', 'count', 'mean_f64', 'std_f64').
         calib: None or ApCalibrate.masters() + exp_ratio (+ pedestal) for the fused path."""
         from .. import ops
-        from .._lib import MAX_STACK
+        from .._lib import MAX_STACK, STACK_REJECT_MAX
         if method not in METHODS:
             raise ValueError(f'Error, stacking method {method} is not one of the allowed methods: {METHODS}')
+        if method in REJECT_METHODS:
+            if frames.shape[0] > STACK_REJECT_MAX:
+                raise ValueError(f'Error, stacking method {method} takes at most {STACK_REJECT_MAX} frames, got {frames.shape[0]}.')
+            return ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
+                                    maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, calib=calib, pixmask=pixmask,
+                                    outputs=outputs)
         if frames.shape[0] > MAX_STACK and method != 'median':
             # beyond what one launch reduces exactly (512 frames): chunks, float64 moments added (ops.stack_sigclip_chunked)
             want = set(outputs) - {'mean', 'count', 'std'}
@@ -116,6 +127,13 @@ class ApStack:
             hdr['STACKITR'] = (-1 if self.maxiters is None else int(self.maxiters), 'Maximum clipping iterations')
             hdr['STACKCEN'] = (self.cenfunc, 'Clipping centre function')
             hdr['STACKDEV'] = (self.stdfunc, 'Clipping deviation function')
+        elif method == 'winsorized':
+            hdr['STACKSGL'] = (float(self.sigma if self.sigma_lower is None else self.sigma_lower), 'Winsorized clip, lower threshold (sigma)')
+            hdr['STACKSGH'] = (float(self.sigma if self.sigma_upper is None else self.sigma_upper), 'Winsorized clip, upper threshold (sigma)')
+            hdr['STACKITR'] = (-1 if self.maxiters is None else int(self.maxiters), 'Maximum clipping rounds')
+        elif method == 'minmax':
+            hdr['STACKNLO'] = (int(self.nlow), 'Lowest values dropped per pixel')
+            hdr['STACKNHI'] = (int(self.nhigh), 'Highest values dropped per pixel')
         for idx, fname in enumerate(input_files):
             hdr[f'IFILE{idx:03d}'] = Path(fname).name
         for k, v in (extra_keywords or {}).items():
@@ -123,6 +141,11 @@ class ApStack:
         tnow = datetime.now().isoformat(timespec='milliseconds')
         hdr['DATE'] = (datetime.now(timezone.utc).isoformat(timespec='seconds'), 'Date/time file was created.')
         hdr['HISTORY'] = f'Processed by {self._name} {__version__} at {tnow}'
+        if method == 'winsorized':
+            hdr['HISTORY'] = (f'Winsorized sigma clip: sigma_lower={hdr["STACKSGL"]} sigma_upper={hdr["STACKSGH"]} '
+                              f'maxiters={hdr["STACKITR"]}')
+        elif method == 'minmax':
+            hdr['HISTORY'] = f'Min/max rejection: nlow={int(self.nlow)} nhigh={int(self.nhigh)}'
         fitsio.write(str(output_file), out, hdr, overwrite=True)
         self._logger.info(f'Wrote stacked image to {output_file}')
         return res

@@ -8,6 +8,7 @@
 namespace apgpu_stack {
 int launch_big(const StackParams &prm, bool u16, bool calib, bool median_only, hipStream_t st, char *describe);   // stack_big.hip
 bool chunks_eligible(const StackParams &prm, bool median_only);                                                  // stack_chunks.hip
+int launch_reject(const apgpu_stack_args *args, hipStream_t st, char *describe);                                 // stack_reject.hip
 }
 
 namespace {
@@ -81,6 +82,36 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
     const bool calib = args->bias != nullptr;
     if (calib && (!args->dark || !args->exp_ratio))
         return fail(APGPU_EINVAL, "stack: fused calibration needs bias, dark and exp_ratio");
+    constexpr int kReject = APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX;
+    if (!median_only && (args->flags & kReject)) {
+        // Winsorized clipping / min-max rejection (stack_reject.hip): one launch, no workspace - `workspace` is not looked at
+        constexpr int kNoEffect = APGPU_STACK_EXACT_MOMENTS | APGPU_STACK_MOMENTS_MEAN | APGPU_STACK_SINGLE_KERNEL;
+        if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED))
+            return fail(APGPU_EINVAL, "stack: unknown flags 0x%x", args->flags);
+        if ((args->flags & kReject) == kReject)
+            return fail(APGPU_EINVAL, "stack: APGPU_STACK_REJECT_WINSORIZED and APGPU_STACK_REJECT_MINMAX exclude each other");
+        if (args->flags & APGPU_STACK_NONFINITE_UNCLIPPED)
+            return fail(APGPU_EINVAL, "stack: APGPU_STACK_NONFINITE_UNCLIPPED does not go with a rejection rule");
+        if (args->center != APGPU_CENTER_MEDIAN || args->dev != APGPU_DEV_STD)
+            return fail(APGPU_EINVAL, "stack: the rejection rules take center = APGPU_CENTER_MEDIAN and dev = APGPU_DEV_STD");
+        if (args->flags & APGPU_STACK_REJECT_MINMAX) {
+            const double lo = args->sigma_lower, hi = args->sigma_upper;
+            if (!(lo >= 0.0 && lo <= 127.0 && hi >= 0.0 && hi <= 127.0) || lo != (double)(int)lo || hi != (double)(int)hi)
+                return fail(APGPU_EINVAL, "stack: min/max rejection drops nlow = sigma_lower and nhigh = sigma_upper values, whole numbers in 0 .. 127");
+        } else {
+            if (args->maxiters == 0) return fail(APGPU_EINVAL, "stack: maxiters must be >= 1 or < 0");
+            if (!(args->sigma_lower >= 0.0) || !(args->sigma_upper >= 0.0))
+                return fail(APGPU_EINVAL, "stack: sigma must be >= 0");
+        }
+        if (args->moments || args->median)
+            return fail(APGPU_EUNSUPPORTED, "stack: the rejection rules give mean, std, count, mean_f64 and std_f64");
+        if (args->n_frames > APGPU_STACK_REJECT_MAX)
+            return fail(APGPU_EUNSUPPORTED, "stack: n_frames = %d exceeds APGPU_STACK_REJECT_MAX = %d (the column of a rejection rule "
+                        "lives in registers)", args->n_frames, APGPU_STACK_REJECT_MAX);
+        if (!args->mean && !args->std && !args->count && !args->mean_f64 && !args->std_f64)
+            return fail(APGPU_EINVAL, "stack: no output requested");
+        return launch_reject(args, as_stream(stream), describe);
+    }
     if (!median_only) {
         if (args->center != APGPU_CENTER_MEDIAN && args->center != APGPU_CENTER_MEAN)
             return fail(APGPU_EINVAL, "stack: bad center %d", args->center);

@@ -372,6 +372,55 @@ def stack_sigclip(frames, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiter
     return res
 
 
+def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=None, nlow=1, nhigh=1,
+                 calib=None, pixmask=None, outputs=('mean',)):
+    """The rejection rules of small stacks (5 .. 30 registered light frames, where an outlier inflates the standard deviation
+    a sigma clip judges it by), per pixel along N, at most _lib.STACK_REJECT_MAX (128) frames; include/apgpu.h has the definition.
+
+    method 'winsorized': rounds of a median-centred clip at sigma_lower / sigma_upper (default: sigma) whose deviation is the
+    Winsorized estimate - the column clamped to median +- 1.5 sig, sig = 1.134 std of that, repeated until it settles;
+    maxiters rounds (None: until a round removes nothing).
+    method 'minmax': the nlow lowest and the nhigh highest values of a column are dropped (ties: by frame index).
+    calib / pixmask: as stack_sigclip.  outputs: any of 'mean', 'std', 'count' (float32 / int32 planes), 'mean_f64', 'std_f64'
+    -> dict of device tensors; the statistics are numpy's of the survivors in frame order, the float32 planes their roundings."""
+    if method not in ('winsorized', 'minmax'):
+        raise ValueError("method must be 'winsorized' or 'minmax', not %r" % (method,))
+    bad = [k for k in outputs if k not in ('mean', 'std', 'count', 'mean_f64', 'std_f64')]
+    if bad or not outputs:
+        raise ValueError('outputs of stack_reject are mean, std, count, mean_f64, std_f64; got %r' % (tuple(outputs),))
+    if frames.dim() < 2:
+        raise ValueError('frames must be [N, ...]')
+    if frames.shape[0] > _lib.STACK_REJECT_MAX:
+        raise ValueError('stack_reject takes at most %d frames (STACK_REJECT_MAX), got %d' % (_lib.STACK_REJECT_MAX, frames.shape[0]))
+    if method == 'minmax':
+        for nm, c in (('nlow', nlow), ('nhigh', nhigh)):
+            if isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= 127:
+                raise ValueError('%s must be a whole number in 0 .. 127, got %r' % (nm, c))
+        lo, hi, mi = float(int(nlow)), float(int(nhigh)), 1
+    else:
+        lo = float(sigma if sigma_lower is None else sigma_lower)
+        hi = float(sigma if sigma_upper is None else sigma_upper)
+        mi = -1 if maxiters is None else int(maxiters)
+        if not (lo >= 0.0 and hi >= 0.0):
+            raise ValueError('sigma must be >= 0')
+        if mi == 0:
+            raise ValueError('maxiters must be >= 1 or None')
+    _need_cuda(frames)
+    lib = _lib.load()
+    keep = []
+    a, N, P, shp, dev = _stack_args(frames, calib, pixmask, keep)
+    a.center, a.dev, a.maxiters = _lib.CENTER['median'], _lib.DEV['std'], mi
+    a.sigma_lower, a.sigma_upper = lo, hi
+    res = {}
+    for k in outputs:
+        res[k] = torch.empty(shp, dtype={'count': torch.int32, 'mean_f64': torch.float64, 'std_f64': torch.float64}.get(k, torch.float32),
+                             device=dev)
+        setattr(a, k, res[k].data_ptr())
+    a.flags = _lib.STACK_REJECT_WINSORIZED if method == 'winsorized' else _lib.STACK_REJECT_MINMAX
+    check(lib.apgpu_stack_sigclip(C.byref(a), _stream()))
+    return res
+
+
 def stack_sigclip_chunked(frames, chunk=None, want_std=False, packed=False, finalize=True, exact=False, **clip):
     """A stack of MORE than APGPU_MAX_STACK (512) frames on one GPU: the frames are reduced in chunks of at most `chunk`
     (default: the largest equal split not above 512), every chunk clipped against its own statistics, and the float64
@@ -454,9 +503,12 @@ def combine_f64(frames, sigma_lower=5.0, sigma_upper=5.0, maxiters=1, cenfunc='m
 
 
 def stack_kernel_name(n_frames, dtype='f32', calibrated=True, outputs=('mean',), median_only=False, stdfunc='std',
-                      moments_mean_only=False, exact=False, maxiters=5):
+                      moments_mean_only=False, exact=False, maxiters=5, rejection=None):
     """Name of the kernel variant the library dispatches for such a stack call (apgpu_stack_kernel_name): what the
-    bench line and the profiles call the dominant kernel.  Needs no device."""
+    bench line and the profiles call the dominant kernel.  Needs no device.  rejection: None, 'winsorized' or 'minmax'
+    (stack_reject)."""
+    if rejection not in (None, 'winsorized', 'minmax'):
+        raise ValueError("rejection must be None, 'winsorized' or 'minmax'")
     lib = _lib.load()
     a = StackArgs()
     a.frames = 0x1000                                     # placeholders: aligned, never dereferenced by the query
@@ -478,6 +530,10 @@ def stack_kernel_name(n_frames, dtype='f32', calibrated=True, outputs=('mean',),
         else:
             setattr(a, k, 0x1000)
     a.flags = (_lib.STACK_EXACT_MOMENTS if exact else 0) | (_lib.STACK_MOMENTS_MEAN if moments_mean_only else 0)
+    if rejection is not None:
+        a.flags |= _lib.STACK_REJECT_WINSORIZED if rejection == 'winsorized' else _lib.STACK_REJECT_MINMAX
+        if rejection == 'minmax':
+            a.sigma_lower = a.sigma_upper = 1.0
     buf = C.create_string_buffer(256)
     check(lib.apgpu_stack_kernel_name(C.byref(a), int(bool(median_only)), buf, 256))
     return buf.value.decode()
@@ -1097,16 +1153,25 @@ def background_weights(frames, fscale=None, sigma=3.0, maxiters=5):
     return 1.0 / (fs * sd) ** 2
 
 
+COADD_COMBINE = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX')
+
+
 def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024,
-          conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False):
+          conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False, nlow=1, nhigh=1):
     """Resample + combine: SWarp's COMBINE_TYPE MEDIAN / AVERAGE / WEIGHTED / SUM (resample_all.sh:60-73 add modes) plus
-    CLIPPED (sigma-clipped mean, median-centred); oversampling = SWarp's OVERSAMPLING.  WEIGHTED takes one weight per frame
+    CLIPPED (sigma-clipped mean, median-centred), WINSORIZED (Winsorized sigma clip at `sigma`, `maxiters` rounds) and MINMAX
+    (the nlow lowest and nhigh highest values of a pixel dropped) - the two rules for stacks of few frames (stack_reject; up to
+    128 frames; fused does not apply); oversampling = SWarp's OVERSAMPLING.  WEIGHTED takes one weight per frame
     (default: background_weights).  Returns dict(image, count[, weight]) - count = frames contributing, weight = the sum
     of their weights (WEIGHTED only).
     fused=True (CLIPPED / AVERAGE, up to 16 frames, oversampling 1): one launch, no [N, h, w] slab of resampled frames in
     memory (resample_stack_sigclip: same survivors; 6.2 against 5.1 ms for C5's share on one MI355X, but 4 N h w bytes less HBM -
     DESIGN 4.4d)."""
     combine = combine.upper()
+    if combine not in COADD_COMBINE:
+        raise ValueError('combine must be one of ' + ', '.join(COADD_COMBINE))
+    if combine in ('WINSORIZED', 'MINMAX') and frames.dim() == 3 and frames.shape[0] > _lib.STACK_REJECT_MAX:
+        raise ValueError('combine %s takes at most %d frames (STACK_REJECT_MAX), got %d' % (combine, _lib.STACK_REJECT_MAX, frames.shape[0]))
     if fused and int(oversampling) == 1 and combine in ('CLIPPED', 'AVERAGE') and frames.dim() == 3 and frames.shape[0] <= 16:
         kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'CLIPPED' else dict(sigma=1e30, maxiters=1, cenfunc='mean')
         r = resample_stack_sigclip(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, n_phases=n_phases,
@@ -1138,7 +1203,11 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     if combine == 'CLIPPED':
         r = stack_sigclip(res, sigma=sigma, maxiters=maxiters, outputs=('mean', 'count'))
         return dict(image=r['mean'], count=r['count'])
-    raise ValueError("combine must be one of MEDIAN, AVERAGE, WEIGHTED, SUM, CLIPPED")
+    if combine == 'WINSORIZED':
+        r = stack_reject(res, 'winsorized', sigma=sigma, maxiters=maxiters, outputs=('mean', 'count'))
+    else:
+        r = stack_reject(res, 'minmax', nlow=nlow, nhigh=nhigh, outputs=('mean', 'count'))
+    return dict(image=r['mean'], count=r['count'])
 
 
 # ---------------------------------------------------------------------------------------------------

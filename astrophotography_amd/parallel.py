@@ -221,7 +221,8 @@ def _record(m, stream):
 
 def stack_nshard(frames_local, calib=None, sigma=3.0, maxiters=5, cenfunc='median', stdfunc='std',
                  n_stripes=None, group=None, local_moments=None, finalize=None, return_moments=False, force_collective=False,
-                 exchange=None, want_std=False, hier_chunk=None, timings=None, exact=False, count_dtype=torch.int32, gather=True):
+                 exchange=None, want_std=False, hier_chunk=None, timings=None, exact=False, count_dtype=torch.int32, gather=True,
+                 rejection=None):
     """N-sharded clipped mean: frames_local[n_local, H, W] on this rank -> mean[H, W] on every rank
     (want_std: (mean, std)).
 
@@ -234,7 +235,13 @@ def stack_nshard(frames_local, calib=None, sigma=3.0, maxiters=5, cenfunc='media
     gather=False ('rs' only, every stripe's rows divisible by the world size): no all-gather - the returned image holds THIS
     rank's rows of every stripe (the rows own_rows(H, n_stripes, world, rank) names) and is undefined elsewhere: 10 bytes per
     pixel x (world - 1) / world leave a rank per step (float16 count) where the gathered form sends 14 and the all-reduce 28.
+    rejection: 'winsorized' / 'minmax' (ops.stack_reject) are refused here: those rules judge a value by its whole column, and
+    a rank only holds its own frames of it - shard by rows instead (stack_rowshard).
     """
+    if rejection is not None:
+        raise ValueError('stack_nshard cannot apply rejection=%r: the Winsorized and min/max rules need all frames of a column '
+                         'together, and a rank holds only its own; shard the rows instead (stack_rowshard(method=%r) + gather_rows)'
+                         % (rejection, rejection))
     if exchange is None:
         exchange = 'rs'
     if exchange not in ('rs', 'f64', 'f32'):
@@ -331,12 +338,16 @@ def own_rows(H, n_stripes, world_size, rank):
 
 
 def stack_rowshard(frames_rows, calib=None, sigma=3.0, maxiters=5, cenfunc='median', stdfunc='std', outputs=('mean',),
-                   method='sigclip'):
+                   method='sigclip', nlow=1, nhigh=1):
     """Exact path: this rank's row block frames_rows[N, h, W] (all N frames; masters in `calib` cut to the same
-    rows) -> its block of the result.  No collective: every output pixel depends only on its own column."""
+    rows) -> its block of the result.  No collective: every output pixel depends only on its own column.
+    method 'winsorized' / 'minmax': the rejection rules of small stacks (ops.stack_reject; cenfunc / stdfunc do not apply)."""
     from . import ops
     if method == 'median':
         return dict(median=ops.stack_median(frames_rows, calib=calib))
+    if method in ('winsorized', 'minmax'):
+        return ops.stack_reject(frames_rows, method, sigma=sigma, maxiters=maxiters, nlow=nlow, nhigh=nhigh, calib=calib,
+                                outputs=outputs)
     return ops.stack_sigclip(frames_rows, sigma=sigma, maxiters=maxiters, cenfunc=cenfunc, stdfunc=stdfunc,
                              calib=calib, outputs=outputs)
 

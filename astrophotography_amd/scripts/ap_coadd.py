@@ -19,8 +19,9 @@ def command_line_opts(argv):
                         help='Per-file 2x3 affine transforms. Default: register through the TAN WCS of the file headers.')
     parser.add_argument('--center', default=None, metavar='RA,DEC', help='Output tangent point in degrees (WCS mode).')
     parser.add_argument('--pixelscale', default=None, type=float, metavar='ARCSEC', help='Output pixel scale (WCS mode).')
-    parser.add_argument('--combine', default='MEDIAN', choices=['MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED'],
-                        help='Combine type (resample_all.sh add modes 0/1/2 = MEDIAN/WEIGHTED/SUM). Default: MEDIAN')
+    parser.add_argument('--combine', default='MEDIAN', choices=['MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX'],
+                        help='Combine type (resample_all.sh add modes 0/1/2 = MEDIAN/WEIGHTED/SUM); WINSORIZED and MINMAX reject '
+                             'outliers in stacks of few frames (at most 128). Default: MEDIAN')
     parser.add_argument('--weight_image', default=None, metavar='WEIGHTS.FITS', help='Optional output weight image.')
     parser.add_argument('--badpix', default=None, metavar='BADPIX.FITS', help='Optional bad pixel mask shared by the inputs.')
     parser.add_argument('--image_size', default=None, metavar='NX,NY', help='Output size (default: input size).')
@@ -28,8 +29,10 @@ def command_line_opts(argv):
                         help='Sub-samples per output pixel and axis (SWarp OVERSAMPLING; resample_all.sh uses 4). Default: 1')
     parser.add_argument('--gain_keyword', default='EGAIN', metavar='KEYWORD',
                         help='Header keyword with the detector gain in e-/ADU (SWarp GAIN_KEYWORD). Default: EGAIN')
-    parser.add_argument('--sigma', default=3.0, type=float, metavar='NSIGMA', help='CLIPPED only.')
-    parser.add_argument('--maxiters', default=5, type=int, metavar='N', help='CLIPPED only; -1 = until convergence.')
+    parser.add_argument('--sigma', default=3.0, type=float, metavar='NSIGMA', help='CLIPPED and WINSORIZED.')
+    parser.add_argument('--maxiters', default=5, type=int, metavar='N', help='CLIPPED and WINSORIZED; -1 = until convergence.')
+    parser.add_argument('--nlow', default=1, type=int, metavar='N', help='MINMAX: lowest values dropped per pixel. Default: 1')
+    parser.add_argument('--nhigh', default=1, type=int, metavar='N', help='MINMAX: highest values dropped per pixel. Default: 1')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
     return parser.parse_args(argv)
 
@@ -57,7 +60,7 @@ def main(args=None):
         nx, ny = (int(v) for v in p.image_size.split(','))
         out_shape = (ny, nx)
     rs = ApResample(p.loglevel, combine=p.combine, sigma=p.sigma, maxiters=None if p.maxiters < 0 else p.maxiters,
-                    oversampling=p.oversampling, gain_keyword=p.gain_keyword)
+                    oversampling=p.oversampling, gain_keyword=p.gain_keyword, nlow=p.nlow, nhigh=p.nhigh)
     center = None
     if p.center:
         center = tuple(float(v) for v in p.center.split(','))

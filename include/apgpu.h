@@ -188,6 +188,38 @@ typedef struct apgpu_stack_args {
  *                               flag non-finite values are masked and the rest is clipped (ccdproc <= 2.1's own loop). */
 #define APGPU_STACK_NONFINITE_UNCLIPPED 8
 
+/* The rejection rules of SMALL stacks (5 .. 30 registered light frames, where an outlier inflates the very standard deviation
+ * a sigma clip judges it by): Winsorized sigma clipping and min/max rejection, through apgpu_stack_sigclip.  The two bits are
+ * mutually exclusive.  With either: one launch, float64 arithmetic, `workspace` is never read or written;
+ * APGPU_STACK_EXACT_MOMENTS, APGPU_STACK_MOMENTS_MEAN and APGPU_STACK_SINGLE_KERNEL are accepted and have no effect;
+ * center must be APGPU_CENTER_MEDIAN and dev APGPU_DEV_STD, APGPU_STACK_NONFINITE_UNCLIPPED is APGPU_EINVAL; outputs are
+ * mean, std, count, mean_f64, std_f64 (`moments` or `median` != NULL: APGPU_EUNSUPPORTED); n_frames <= APGPU_STACK_REJECT_MAX
+ * (the column lives in registers; more: APGPU_EUNSUPPORTED).  Both dtypes, the fused calibration, pixmask and frame_stride
+ * work as without the bits.  apgpu_resample_stack_sigclip does not serve them (APGPU_EUNSUPPORTED).
+ *
+ * Per pixel: S = the finite values of the column after the optional calibration (float32 values), widened to float64, in frame
+ * order.  A masked pixel or an empty S gives NaN (0x7fc00000) and count 0.  No contraction: every multiply and add rounds.
+ *   APGPU_STACK_REJECT_WINSORIZED (kl = sigma_lower, kh = sigma_upper, both >= 0; maxiters rounds, < 0 = until a round removes
+ *   nothing):
+ *     round:  n = len(S); if n < 3: stop
+ *             med = np.median(S); sig = np.std(S)                      (ddof 0, numpy's summation order)
+ *             repeat at most APGPU_STACK_WINSOR_MAX_INNER times:
+ *                 W   = min(max(S, med - 1.5*sig), med + 1.5*sig)      (clamped from S each time, never from the previous W)
+ *                 s0  = sig; sig = 1.134 * np.std(W)
+ *                 if |sig - s0| <= 0.0005 * s0: break
+ *             keep x with  med - kl*sig <= x <= med + kh*sig           (inclusive)
+ *             if nothing was removed: stop;  S = the kept values, still in frame order
+ *     np.median of an even count: the two middle values summed from +0 and halved.
+ *   APGPU_STACK_REJECT_MINMAX (nlow = sigma_lower, nhigh = sigma_upper: whole numbers 0 .. 127 held as doubles, else
+ *   APGPU_EINVAL; maxiters unused): order S by (order-preserving key of the value: -0 below +0, then frame index), drop the first
+ *     nlow and the last nhigh; n <= nlow + nhigh: nothing survives.
+ *   Outputs over the survivors in frame order: count = m, mean_f64 = np.add.reduce(surv) / m, std_f64 = np.std(surv); mean and
+ *   std are those values rounded once to float32. */
+#define APGPU_STACK_REJECT_WINSORIZED 16
+#define APGPU_STACK_REJECT_MINMAX 32
+#define APGPU_STACK_REJECT_MAX 128
+#define APGPU_STACK_WINSOR_MAX_INNER 16
+
 /* The two-kernel scheme and its workspace.  A clipped stack of up to 128 frames (and the chunked kernel for 129 .. 512) with
  * lean outputs runs as a FAST kernel - the float32 fast path alone, four wavefronts per SIMD - followed by a REDO PASS of the
  * complete kernel over what the fast kernel could not finish: single pixels (unsure comparisons, non-finite values, masked
