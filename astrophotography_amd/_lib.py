@@ -16,6 +16,7 @@ DEV = {'std': 0, 'mad_std': 1}
 MAX_STACK = 512
 STACK_EXACT_MOMENTS, STACK_MOMENTS_MEAN, STACK_SINGLE_KERNEL, STACK_NONFINITE_UNCLIPPED = 1, 2, 4, 8    # apgpu_stack_args.flags
 STACK_REJECT_WINSORIZED, STACK_REJECT_MINMAX = 16, 32   # apgpu_stack_args.flags: the rejection rules of small stacks (ops.stack_reject)
+STACK_FRAME_PARAMS = 64                                 # APGPU_STACK_FRAME_PARAMS: exp_ratio = float32 [3][N] scale, offset, weight (with a rejection rule)
 STACK_REJECT_MAX = 128                                  # APGPU_STACK_REJECT_MAX: frames a rejection rule takes
 CCDPROC_FORM = {'astropy': 0, 'legacy': 1}                                  # APGPU_CCDPROC_*
 STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_OFFSET: int64 calls, pixels, pixels listed, 64-pixel blocks given up

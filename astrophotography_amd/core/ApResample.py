@@ -18,11 +18,12 @@ from .. import __version__, fitsio
 from . import _common
 
 COMBINE_TYPES = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX')
+NORMALIZE_MODES = ('none', 'additive', 'multiplicative', 'additive+scaling')
 
 
 class ApResample:
     def __init__(self, loglevel='INFO', combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024, conserve_flux=True, oversampling=1,
-                 gain_keyword='EGAIN', nlow=1, nhigh=1):
+                 gain_keyword='EGAIN', nlow=1, nhigh=1, normalize='none', reference=0, weighting=None):
         self._name = 'ApResample'
         self._logger = _common.make_logger(self._name, loglevel)
         combine = str(combine).upper()
@@ -35,11 +36,29 @@ class ApResample:
         self.gain_keyword = gain_keyword                    # GAIN_KEYWORD (resample_all.sh:111: EGAIN)
         if not 1 <= self.oversampling <= 16:
             raise ValueError(f'Error, oversampling {oversampling} is not in 1..16')
+        # normalisation of the resampled frames to the reference frame's level before the combine (ops.frame_normalization)
+        normalize = 'none' if normalize is None else str(normalize).lower()
+        if normalize not in NORMALIZE_MODES:
+            raise ValueError(f'Error, normalize {normalize} is not one of the allowed modes: {NORMALIZE_MODES}')
+        weighting = None if weighting in (None, 'none') else str(weighting).lower()
+        if weighting not in (None, 'noise'):
+            raise ValueError(f"Error, weighting {weighting} is not one of: none, noise")
+        if weighting is not None and combine not in ('WINSORIZED', 'MINMAX'):
+            raise ValueError(f'Error, weighting {weighting} goes with combine WINSORIZED and MINMAX only, not {combine}.')
+        self.normalize, self.weighting = normalize, weighting
+        self.reference = reference                          # a frame index, or (coadd_files) a file name
 
-    def coadd(self, frames, affines, fscale=None, mask=None, out_shape=None, weights=None, fine_affines=None, fused=False):
+    def coadd(self, frames, affines, fscale=None, mask=None, out_shape=None, weights=None, fine_affines=None, fused=False, reference=None):
         """frames [N,H,W] float32 device tensor -> dict(image, count[, weight]) device tensors.  fused: ops.coadd's one-launch
-        form (CLIPPED / AVERAGE of up to 16 frames, no resampled slab in memory)."""
+        form (CLIPPED / AVERAGE of up to 16 frames, no resampled slab in memory).  With a normalisation the result also holds
+        scale, offset and norm_weights per frame; reference: the frame index (default: the constructor's)."""
         from .. import ops
+        if self.normalize != 'none' or self.weighting is not None:
+            ref = self.reference if reference is None else reference
+            return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
+                             sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
+                             oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
+                             nlow=self.nlow, nhigh=self.nhigh, normalize=self.normalize, reference=int(ref), weighting=self.weighting)
         return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                          sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
                          oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
@@ -58,6 +77,22 @@ class ApResample:
             return float(1.0 / np.sum(1.0 / g))
         w = np.ones(len(g)) if weights is None or self.combine != 'WEIGHTED' else np.asarray(weights, dtype=np.float64)
         return float(np.sum(w) ** 2 / np.sum(w * w / g))
+
+    def _reference_index(self, input_files):
+        """self.reference as a frame index: an index, or the name (or base name) of one of the input files."""
+        ref = self.reference
+        if isinstance(ref, str) and not ref.lstrip('-').isdigit():
+            names = [str(f) for f in input_files]
+            for cand in (names, [Path(f).name for f in names]):
+                if ref in cand:
+                    return cand.index(ref)
+                if Path(ref).name in cand:
+                    return cand.index(Path(ref).name)
+            raise RuntimeError(f'Error, reference {ref} is not one of the input files.')
+        ref = int(ref)
+        if not 0 <= ref < len(input_files):
+            raise RuntimeError(f'Error, reference {ref} is not a file index (0 .. {len(input_files) - 1}).')
+        return ref
 
     def _exposure(self, hdr, fname):
         for kw in ('EXPOSURE', 'EXPTIME'):                   # same order as resample_all.sh:283-297
@@ -131,8 +166,9 @@ class ApResample:
             weights = ops.background_weights(slab, np.asarray(fscale, np.float64))
             for f, wgt in zip(input_files, weights):
                 self._logger.info(f'  File {Path(f).name:40s} WEIGHT {wgt:12.6g}')
+        ref = self._reference_index(input_files)
         res = self.coadd(slab, affines, fscale=np.asarray(fscale, np.float32), mask=mask, out_shape=out_shape, weights=weights,
-                         fine_affines=fine_affines)
+                         fine_affines=fine_affines, reference=ref)
         hdr = hdrs[0].copy()
         for kw in ('BSCALE', 'BZERO', 'PEDESTAL'):
             if kw in hdr:
@@ -145,6 +181,16 @@ class ApResample:
         elif self.combine == 'MINMAX':
             hdr['COMBNLO'] = (self.nlow, 'Lowest values dropped per pixel')
             hdr['COMBNHI'] = (self.nhigh, 'Highest values dropped per pixel')
+        if 'scale' in res:
+            hdr['NORMMODE'] = (self.normalize, 'Frame normalisation before the combine')
+            hdr['NORMREF'] = (Path(input_files[ref]).name, 'Reference frame of the normalisation')
+            hdr['NORMWGT'] = (self.weighting or 'none', 'Weighting of the surviving values')
+            for idx, fname in enumerate(input_files):
+                a, b, w = float(res['scale'][idx]), float(res['offset'][idx]), float(res['norm_weights'][idx])
+                hdr[f'NSCL{idx:03d}'] = (a, 'Normalisation scale of IFILE%03d' % idx)
+                hdr[f'NOFF{idx:03d}'] = (b, 'Normalisation offset of IFILE%03d' % idx)
+                hdr[f'NWGT{idx:03d}'] = (w, 'Weight of IFILE%03d' % idx)
+                self._logger.info(f'  File {Path(fname).name:40s} NSCALE {a:10.6f} NOFFSET {b:12.6g} NWEIGHT {w:8.6f}')
         hdr['RESAMPT'] = ('LANCZOS3', 'Resampling kernel')
         hdr['OVERSAMP'] = (self.oversampling, 'Sub-samples per output pixel and axis')
         gain_out = self._output_gain(gains, fscale, weights)

@@ -41,22 +41,39 @@ class ApStack:
         self.maxiters, self.cenfunc, self.stdfunc = maxiters, cenfunc, stdfunc
         self.nlow, self.nhigh = nlow, nhigh
 
-    def stack(self, frames, method='sigclip', calib=None, pixmask=None, outputs=('mean',)):
+    def stack(self, frames, method='sigclip', calib=None, pixmask=None, outputs=('mean',), normalize='none', reference=0,
+              weighting=None):
         """frames[N,H,W] device tensor (uint16|float32) -> dict of device tensors.
 
         method 'sigclip': clipped mean (+ 'median', 'std', 'count', 'moments' planes on request);
         'mean': plain mean (a clip with an infinite bound, one pass); 'median': np.nanmedian along N;
         'winsorized': Winsorized sigma clip at sigma / sigma_lower / sigma_upper, maxiters rounds, and 'minmax': the nlow
         lowest and nhigh highest values of a pixel dropped - the rules for 5 .. 30 frames, at most 128 (ops.stack_reject;
-        outputs 'mean', 'std', 'count', 'mean_f64', 'std_f64').
+        outputs 'mean', 'std', 'count', 'mean_f64', 'std_f64').  Those two take normalize ('additive', 'multiplicative',
+        'additive+scaling': the frames brought to frame `reference`'s level inside the kernel, ops.frame_stats /
+        ops.frame_normalization) and weighting='noise' (the survivors averaged with inverse-variance weights) on a slab that is
+        not calibrated in the same call; the result then also holds scale, offset and norm_weights (float64 numpy [N]).
         calib: None or ApCalibrate.masters() + exp_ratio (+ pedestal) for the fused path."""
         from .. import ops
         from .._lib import MAX_STACK, STACK_REJECT_MAX
         if method not in METHODS:
             raise ValueError(f'Error, stacking method {method} is not one of the allowed methods: {METHODS}')
+        normed = normalize not in (None, 'none') or weighting not in (None, 'none')
+        if normed and method not in REJECT_METHODS:
+            raise ValueError(f'Error, normalize / weighting go with the methods {REJECT_METHODS}, not {method}.')
         if method in REJECT_METHODS:
             if frames.shape[0] > STACK_REJECT_MAX:
                 raise ValueError(f'Error, stacking method {method} takes at most {STACK_REJECT_MAX} frames, got {frames.shape[0]}.')
+            if normed:
+                if calib is not None:
+                    raise ValueError('Error, normalize / weighting need calibrated frames: they do not go with the fused calibration.')
+                a, b, w = ops.frame_normalization(ops.frame_stats(frames), normalize or 'none', reference=reference,
+                                                  weighting=None if weighting in (None, 'none') else weighting)
+                res = ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
+                                       maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, pixmask=pixmask, outputs=outputs,
+                                       scale=a, offset=b, weights=w)
+                res.update(scale=a, offset=b, norm_weights=w)
+                return res
             return ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
                                     maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, calib=calib, pixmask=pixmask,
                                     outputs=outputs)

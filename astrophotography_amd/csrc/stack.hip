@@ -83,11 +83,22 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
     if (calib && (!args->dark || !args->exp_ratio))
         return fail(APGPU_EINVAL, "stack: fused calibration needs bias, dark and exp_ratio");
     constexpr int kReject = APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX;
+    if ((args->flags & APGPU_STACK_FRAME_PARAMS) && (median_only || !(args->flags & kReject)))
+        return fail(APGPU_EUNSUPPORTED, "stack: APGPU_STACK_FRAME_PARAMS is served by the rejection rules only (APGPU_STACK_REJECT_WINSORIZED "
+                    "or APGPU_STACK_REJECT_MINMAX of apgpu_stack_sigclip)");
     if (!median_only && (args->flags & kReject)) {
         // Winsorized clipping / min-max rejection (stack_reject.hip): one launch, no workspace - `workspace` is not looked at
         constexpr int kNoEffect = APGPU_STACK_EXACT_MOMENTS | APGPU_STACK_MOMENTS_MEAN | APGPU_STACK_SINGLE_KERNEL;
-        if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED))
+        if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED | APGPU_STACK_FRAME_PARAMS))
             return fail(APGPU_EINVAL, "stack: unknown flags 0x%x", args->flags);
+        if (args->flags & APGPU_STACK_FRAME_PARAMS) {
+            // exp_ratio is float32 [3][n_frames]: scale, offset, weight of every frame; light frames are calibrated already
+            if (args->bias || args->dark || args->nflat || args->pedestal)
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_PARAMS excludes the fused calibration (bias, dark, nflat and pedestal must be NULL)");
+            if (!args->exp_ratio)
+                return fail(APGPU_EINVAL, "stack: unknown flags 0x%x for a call without exp_ratio: APGPU_STACK_FRAME_PARAMS needs exp_ratio = "
+                            "float32 [3][n_frames] (scale, offset, weight)", args->flags);
+        }
         if ((args->flags & kReject) == kReject)
             return fail(APGPU_EINVAL, "stack: APGPU_STACK_REJECT_WINSORIZED and APGPU_STACK_REJECT_MINMAX exclude each other");
         if (args->flags & APGPU_STACK_NONFINITE_UNCLIPPED)

@@ -19,6 +19,9 @@
 //     first nlow and the last nhigh; n <= nlow + nhigh leaves nothing.
 //   Outputs over the survivors in frame order: count = m, mean_f64 = np.add.reduce(surv) / m, std_f64 = np.std(surv), mean and
 //   std those values rounded once to float32.
+//   APGPU_STACK_FRAME_PARAMS (exp_ratio = float32 [3][N]: scale a, offset b, weight w; no calibration): the column is
+//   v = float32(float32(a_i x) + b_i), the rule runs on the finite v, count and std_f64 as above (unweighted), and
+//   mean_f64 = num / den, num += double(w_k) double(v_k), den += double(w_k) over the survivors in frame order from +0.0.
 //
 // THE KERNEL.  One pixel per lane, one wavefront per workgroup, the column v[NP] in VGPRs IN FRAME ORDER and COMPACT: v[0 .. n)
 // are the lane's current S, v[n .. NP) are NaN.  numpy's sum of n <= 128 terms puts term i into accumulator i % 8 (i < n - n % 8)
@@ -209,9 +212,15 @@ __device__ __forceinline__ double np_pass(const float (&v)[NP], int n, int nmin8
     return 0.0 + res;                                        // np.add.reduce folds its pieces from +0: a sum of -0s is +0
 }
 
-template <int NP, typename RawT, bool CALIB>
+// v = float32(float32(a x) + b): the map of APGPU_STACK_FRAME_PARAMS, each operation rounded on its own
+__device__ __forceinline__ float frame_map(float x, float a, float b) { return __fadd_rn(__fmul_rn(a, x), b); }
+
+// FP: APGPU_STACK_FRAME_PARAMS - prm.exp_ratio is float32 [3][N] = scale a, offset b, weight w of every frame; the column is
+// v = a x + b (two roundings) and the mean is the weighted mean of the survivors (see the end).  No calibration then.
+template <int NP, typename RawT, bool CALIB, bool FP = false>
 __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm)
 {
+    static_assert(!(CALIB && FP), "fused calibration and frame parameters exclude each other");
     __shared__ float cols[NP * 64];
     const int lane = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * 64;
@@ -263,6 +272,7 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
                     x = x - ds;                              // :451
                     if (dodiv) x = __fdiv_rn(x, nf);         // :463
                 }
+                if constexpr (FP) x = frame_map(x, prm.exp_ratio[f], prm.exp_ratio[N + f]);
                 v[j + k] = j + k < N ? x : quiet_nan();
             }
         }
@@ -278,6 +288,12 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
     }
 
     // ---- min/max: the bounds are the keys of rank nlow - 1 and n - nhigh; equal keys go by frame index ----
+    // (FP) the membership test of the rule, kept for the weighted walk over the frames at the end: min/max - the two key bounds
+    // and the tie counts; Winsorized - the intersection [Lo, Hi] of the rounds' intervals
+    unsigned mm_klo = 0, mm_khi = 0xffffffffu;               // (an end the rule does not trim: bounds and counts no value fails)
+    int mm_dlo = 0, mm_keephi = NP + 1;
+    bool mm_some = true;
+    double Lo = -inf, Hi = inf;
     if (prm.minmax) {
         const int nlow = prm.nlow, nhigh = prm.nhigh;
         const int nmax = wave_max_i(n);
@@ -305,6 +321,10 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
             const int dlo = nlow > 0 ? nlow - lt : 0;
             const int keephi = nhigh > 0 ? eqhi - (nhigh - gt) : NP + 1;
             const bool uselo = nlow > 0, usehi = nhigh > 0;
+            if constexpr (FP) {
+                mm_klo = uselo ? klo : 0u; mm_khi = usehi ? khi : 0xffffffffu;
+                mm_dlo = dlo; mm_keephi = keephi; mm_some = some;
+            }
             int seenlo = 0, seenhi = 0;
             const int nn = n;
             n = compact<NP>(v, col, nmax, [&](int i) {
@@ -381,6 +401,10 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
             } else {
                 // the clip of this round (lanes without a round keep everything)
                 const double lo = active ? med - kl * sig : -inf, hi = active ? med + kh * sig : inf;
+                if constexpr (FP) {                          // (a lane without a round has -inf / +inf: no change)
+                    Lo = !(lo <= Lo) ? lo : Lo;              // (a NaN bound - sigma = inf on a constant column - keeps
+                    Hi = !(hi >= Hi) ? hi : Hi;              //  nothing, here as in the round)
+                }
                 int kept = 0;
 #pragma unroll
                 for (int j = 0; j < NP; j += 8) {
@@ -411,6 +435,52 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
         }
     }
 
+    // ---- (FP) the weighted mean.  The compact column has lost its frame indices, so the frames are walked once more from memory
+    // (the kernel is bound by its arithmetic many times over): v is formed again, the rule's membership test is
+    // repeated on it - Winsorized: finite and inside [Lo, Hi], for a removed value lies outside its round's interval and a kept one
+    // inside every round's; min/max: the two key bounds and the tie counters over the finite values in frame order, as the
+    // compaction above counted them - and num += double(w) double(v), den += double(w) run in frame order from +0.
+    if constexpr (FP) {
+        const int off = valid ? lane : 0;
+        const RawT *const fb = static_cast<const RawT *>(prm.frames) + base + off;
+        const bool mm = prm.minmax != 0;
+        double num = 0.0, den = 0.0;
+        int seenlo = 0, seenhi = 0;
+        constexpr int B = 8;                                 // frames per block: eight loads in flight, as on the first load
+#pragma unroll 1
+        for (int j = 0; j < N; j += B) {
+            RawT raw[B];
+#pragma unroll
+            for (int k = 0; k < B; k++) {
+                const int f = j + k < N ? j + k : N - 1;
+                raw[k] = fb[(int64_t)f * prm.stride];
+            }
+#pragma unroll
+            for (int k = 0; k < B; k++) {
+                const int f = j + k < N ? j + k : N - 1;
+                const float x = frame_map(to_f32(raw[k]), prm.exp_ratio[f], prm.exp_ratio[N + f]);
+                const float w = prm.exp_ratio[2 * N + f];
+                const bool fin = j + k < N && is_finite(x);
+                bool ok;
+                if (mm) {                                    // (wave-uniform)
+                    const unsigned key = OrderKey<float>::to(x);
+                    const bool elo = key == mm_klo, ehi = key == mm_khi;
+                    ok = fin && mm_some && key >= mm_klo && (!elo || seenlo >= mm_dlo) && key <= mm_khi && (!ehi || seenhi < mm_keephi);
+                    seenlo += (elo && fin) ? 1 : 0;
+                    seenhi += (ehi && fin) ? 1 : 0;
+                } else {
+                    const double xd = widen(x);
+                    ok = fin && xd >= Lo && xd <= Hi;
+                }
+                const double wd = widen(w);
+                const double t = wd * widen(x);              // (exact: two widened float32 values)
+                num = ok ? num + t : num;
+                den = ok ? den + wd : den;
+            }
+        }
+        mean = num / den;
+    }
+
     if (valid) {
         const bool any = n > 0;
         const double nan64 = __builtin_nan("");
@@ -422,23 +492,24 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
     }
 }
 
-template <int NP, typename RawT, bool CALIB>
+template <int NP, typename RawT, bool CALIB, bool FP>
 int launch_one(const RejectParams &prm, hipStream_t st, char *describe)
 {
     if (describe) {
-        snprintf(describe, 256, "stack_reject_kernel<%d, %s, %s>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float", CALIB ? "true" : "false");
+        if (FP) snprintf(describe, 256, "stack_reject_kernel<%d, %s, false, true>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float");
+        else snprintf(describe, 256, "stack_reject_kernel<%d, %s, %s>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float", CALIB ? "true" : "false");
         return APGPU_OK;
     }
     const int64_t grid = (prm.P + 63) / 64;
     if (grid > 0x7fffffff) return fail(APGPU_EUNSUPPORTED, "stack (reject): n_pixels = %lld is too many for one launch", (long long)prm.P);
-    hipLaunchKernelGGL((stack_reject_kernel<NP, RawT, CALIB>), dim3((unsigned)grid), dim3(64), 0, st, prm);
+    hipLaunchKernelGGL((stack_reject_kernel<NP, RawT, CALIB, FP>), dim3((unsigned)grid), dim3(64), 0, st, prm);
     return check_launch("stack kernel (reject)");
 }
 
-template <typename RawT, bool CALIB>
+template <typename RawT, bool CALIB, bool FP = false>
 int launch_slots(const RejectParams &prm, hipStream_t st, char *describe)
 {
-#define APGPU_REJECT_TRY(NP) if (prm.N <= NP) return launch_one<NP, RawT, CALIB>(prm, st, describe);
+#define APGPU_REJECT_TRY(NP) if (prm.N <= NP) return launch_one<NP, RawT, CALIB, FP>(prm, st, describe);
     APGPU_REJECT_SLOTS(APGPU_REJECT_TRY)
 #undef APGPU_REJECT_TRY
     return fail(APGPU_EUNSUPPORTED, "stack (reject): n_frames = %d exceeds APGPU_STACK_REJECT_MAX = %d", prm.N, APGPU_STACK_REJECT_MAX);
@@ -477,6 +548,8 @@ int launch_reject(const apgpu_stack_args *args, hipStream_t st, char *describe)
         prm.kl = args->sigma_lower;
         prm.kh = args->sigma_upper;
     }
+    if (args->flags & APGPU_STACK_FRAME_PARAMS)              // (no calibration planes: stack_dispatch has seen to it)
+        return args->dtype == APGPU_F32 ? launch_slots<float, false, true>(prm, st, describe) : launch_slots<uint16_t, false, true>(prm, st, describe);
     const bool calib = args->bias != nullptr;
     if (args->dtype == APGPU_F32) return calib ? launch_slots<float, true>(prm, st, describe) : launch_slots<float, false>(prm, st, describe);
     return calib ? launch_slots<uint16_t, true>(prm, st, describe) : launch_slots<uint16_t, false>(prm, st, describe);

@@ -373,7 +373,7 @@ def stack_sigclip(frames, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiter
 
 
 def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=None, nlow=1, nhigh=1,
-                 calib=None, pixmask=None, outputs=('mean',)):
+                 calib=None, pixmask=None, outputs=('mean',), scale=None, offset=None, weights=None):
     """The rejection rules of small stacks (5 .. 30 registered light frames, where an outlier inflates the standard deviation
     a sigma clip judges it by), per pixel along N, at most _lib.STACK_REJECT_MAX (128) frames; include/apgpu.h has the definition.
 
@@ -382,7 +382,11 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
     maxiters rounds (None: until a round removes nothing).
     method 'minmax': the nlow lowest and the nhigh highest values of a column are dropped (ties: by frame index).
     calib / pixmask: as stack_sigclip.  outputs: any of 'mean', 'std', 'count' (float32 / int32 planes), 'mean_f64', 'std_f64'
-    -> dict of device tensors; the statistics are numpy's of the survivors in frame order, the float32 planes their roundings."""
+    -> dict of device tensors; the statistics are numpy's of the survivors in frame order, the float32 planes their roundings.
+    scale / offset / weights (APGPU_STACK_FRAME_PARAMS; all None: not used): one value per frame, missing ones 1 / 0 / 1.  The
+    rule then runs on v = float32(float32(scale_i x) + offset_i), and the mean is sum w_i v_i / sum w_i over the survivors
+    (float64, frame order); std and count stay unweighted.  Not together with calib; see frame_normalization."""
+    fp = _frame_params(frames, scale, offset, weights, calib)
     if method not in ('winsorized', 'minmax'):
         raise ValueError("method must be 'winsorized' or 'minmax', not %r" % (method,))
     bad = [k for k in outputs if k not in ('mean', 'std', 'count', 'mean_f64', 'std_f64')]
@@ -417,8 +421,108 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
                              device=dev)
         setattr(a, k, res[k].data_ptr())
     a.flags = _lib.STACK_REJECT_WINSORIZED if method == 'winsorized' else _lib.STACK_REJECT_MINMAX
+    if fp is not None:
+        block = torch.from_numpy(fp).to(dev)                 # float32 [3, N]: scale, offset, weight
+        keep.append(block)
+        a.exp_ratio = block.data_ptr()
+        a.flags |= _lib.STACK_FRAME_PARAMS
     check(lib.apgpu_stack_sigclip(C.byref(a), _stream()))
     return res
+
+
+def _frame_params(frames, scale, offset, weights, calib):
+    """The float32 [3, N] block of APGPU_STACK_FRAME_PARAMS on the host, checked (the library cannot look at device values);
+    None when none of the three is given."""
+    if scale is None and offset is None and weights is None:
+        return None
+    if calib is not None:
+        raise ValueError('scale / offset / weights do not go with calib: frame parameters are for calibrated light frames')
+    if frames.dim() < 2:
+        raise ValueError('frames must be [N, ...]')
+    N = frames.shape[0]
+    block = np.empty((3, N), dtype=np.float32)
+    for row, (nm, x, default) in enumerate((('scale', scale, 1.0), ('offset', offset, 0.0), ('weights', weights, 1.0))):
+        if x is None:
+            block[row] = default
+            continue
+        if torch.is_tensor(x):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        if x.size != N:
+            raise ValueError('%s must hold one value per frame (%d), got %d' % (nm, N, x.size))
+        with np.errstate(over='ignore'):
+            block[row] = x.astype(np.float32)
+        if not np.isfinite(block[row]).all():
+            raise ValueError('%s must be finite (as float32)' % nm)
+    if not (block[2] > 0).all():
+        raise ValueError('weights must be > 0 (as float32)')
+    return block
+
+
+def frame_stats(frames, sigma=3.0, maxiters=5):
+    """Per frame, the sigma-clipped median and standard deviation of its finite values (the A3 kernels, sigclip_global): what
+    frame_normalization takes as a frame's location and scale.  All N reductions are queued without a host synchronisation in
+    between.  Returns a float64 [N, 2] device tensor (median, std); a frame without a finite pixel has NaN."""
+    _need_cuda(frames)
+    if frames.dim() < 2:
+        raise ValueError('frames must be [N, ...]')
+    N = frames.shape[0]
+    out = torch.empty((N, 2), dtype=torch.float64, device=frames.device)
+    for i in range(N):
+        out[i] = sigclip_global(frames[i], sigma=sigma, maxiters=maxiters)[1:3]
+    return out
+
+
+NORMALIZE_MODES = ('none', 'additive', 'multiplicative', 'additive+scaling')
+
+
+def frame_normalization(stats, mode, reference=0, weighting=None):
+    """Per-frame (scale a, offset b, weights w) - float64 numpy [N] each - that bring frames to the reference frame's level:
+    v = a x + b.  stats: [N, 2] location L and scale S of every frame (frame_stats; a device tensor costs one copy to the host).
+
+        'additive'            a = 1           b = L_r - L_i
+        'multiplicative'      a = L_r / L_i   b = 0                  (every L > 0)
+        'additive+scaling'    a = S_r / S_i   b = L_r - a L_i
+        'none'                a = 1           b = 0
+
+    weighting 'noise': w_i = 1 / (a_i S_i)^2 divided by the largest (0 < w <= 1); None (or 'none'): ones."""
+    if mode not in NORMALIZE_MODES:
+        raise ValueError('normalize must be one of ' + ', '.join(NORMALIZE_MODES) + ', not %r' % (mode,))
+    if weighting not in (None, 'none', 'noise'):
+        raise ValueError("weighting must be None or 'noise', not %r" % (weighting,))
+    st = stats.detach().cpu().numpy() if torch.is_tensor(stats) else np.asarray(stats)
+    st = np.asarray(st, dtype=np.float64)
+    if st.ndim != 2 or st.shape[1] != 2 or st.shape[0] < 1:
+        raise ValueError('stats must be [N, 2] (location, scale)')
+    N = st.shape[0]
+    r = int(reference)
+    if not 0 <= r < N:
+        raise ValueError('reference = %d is not a frame index (N = %d)' % (r, N))
+    L, S = st[:, 0], st[:, 1]
+    need_L = mode != 'none'
+    need_S = mode == 'additive+scaling' or weighting == 'noise'
+    for i in range(N):
+        if (need_L and not np.isfinite(L[i])) or (need_S and not np.isfinite(S[i])):
+            raise ValueError('frame %d has no finite pixel: no statistics to normalise it by' % i)
+        if need_S and not S[i] > 0:
+            raise ValueError('frame %d has scale S = %g (a constant frame): it cannot be scaled or weighted by its noise' % (i, S[i]))
+        if mode == 'multiplicative' and not L[i] > 0:
+            raise ValueError('frame %d has location L = %g: multiplicative normalisation needs every L > 0' % (i, L[i]))
+    if mode == 'additive':
+        a, b = np.ones(N), L[r] - L
+    elif mode == 'multiplicative':
+        a, b = L[r] / L, np.zeros(N)
+    elif mode == 'additive+scaling':
+        a = S[r] / S
+        b = L[r] - a * L
+    else:
+        a, b = np.ones(N), np.zeros(N)
+    if weighting == 'noise':
+        w = 1.0 / (a * S) ** 2
+        w = w / w.max()
+    else:
+        w = np.ones(N)
+    return a, b, w
 
 
 def stack_sigclip_chunked(frames, chunk=None, want_std=False, packed=False, finalize=True, exact=False, **clip):
@@ -1157,7 +1261,8 @@ COADD_COMBINE = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED'
 
 
 def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024,
-          conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False, nlow=1, nhigh=1):
+          conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False, nlow=1, nhigh=1,
+          normalize='none', reference=0, weighting=None):
     """Resample + combine: SWarp's COMBINE_TYPE MEDIAN / AVERAGE / WEIGHTED / SUM (resample_all.sh:60-73 add modes) plus
     CLIPPED (sigma-clipped mean, median-centred), WINSORIZED (Winsorized sigma clip at `sigma`, `maxiters` rounds) and MINMAX
     (the nlow lowest and nhigh highest values of a pixel dropped) - the two rules for stacks of few frames (stack_reject; up to
@@ -1166,10 +1271,29 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     of their weights (WEIGHTED only).
     fused=True (CLIPPED / AVERAGE, up to 16 frames, oversampling 1): one launch, no [N, h, w] slab of resampled frames in
     memory (resample_stack_sigclip: same survivors; 6.2 against 5.1 ms for C5's share on one MI355X, but 4 N h w bytes less HBM -
-    DESIGN 4.4d)."""
+    DESIGN 4.4d).
+    normalize ('none', 'additive', 'multiplicative', 'additive+scaling'; frame_normalization) brings the resampled frames to
+    the level of frame `reference` before they are combined: the statistics (frame_stats) are taken on the resampled slab -
+    those are the values that get compared.  WINSORIZED / MINMAX apply v = a x + b inside the kernel (stack_reject) and take
+    weighting='noise' (the survivors' mean weighted by 1 / (a S)^2); the other modes get the same float32 map on the slab
+    in place and take no weighting (WEIGHTED has `weights`).  The result then also holds scale, offset and norm_weights
+    (float64 numpy [N])."""
     combine = combine.upper()
     if combine not in COADD_COMBINE:
         raise ValueError('combine must be one of ' + ', '.join(COADD_COMBINE))
+    if normalize is None:
+        normalize = 'none'
+    if weighting == 'none':
+        weighting = None
+    if normalize not in NORMALIZE_MODES:
+        raise ValueError('normalize must be one of ' + ', '.join(NORMALIZE_MODES) + ', not %r' % (normalize,))
+    if weighting not in (None, 'noise'):
+        raise ValueError("weighting must be None or 'noise', not %r" % (weighting,))
+    if weighting is not None and combine not in ('WINSORIZED', 'MINMAX'):
+        raise ValueError('weighting goes with combine WINSORIZED and MINMAX only (WEIGHTED takes weights), not with %s' % combine)
+    normed = normalize != 'none' or weighting is not None
+    if fused and normed:
+        raise ValueError('fused=True does not go with a normalisation: the statistics are taken on the resampled slab')
     if combine in ('WINSORIZED', 'MINMAX') and frames.dim() == 3 and frames.shape[0] > _lib.STACK_REJECT_MAX:
         raise ValueError('combine %s takes at most %d frames (STACK_REJECT_MAX), got %d' % (combine, _lib.STACK_REJECT_MAX, frames.shape[0]))
     if fused and int(oversampling) == 1 and combine in ('CLIPPED', 'AVERAGE') and frames.dim() == 3 and frames.shape[0] <= 16:
@@ -1183,6 +1307,25 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     else:
         res, _ = resample_affine(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, n_phases=n_phases, weight=False,
                                  conserve_flux=conserve_flux)
+    if normed:
+        a, b, w = frame_normalization(frame_stats(res, sigma=3.0, maxiters=5), normalize, reference=reference, weighting=weighting)
+        extra = dict(scale=a, offset=b, norm_weights=w)
+        if combine in ('WINSORIZED', 'MINMAX'):
+            kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'WINSORIZED' else dict(nlow=nlow, nhigh=nhigh)
+            r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, **kw)
+            return dict(image=r['mean'], count=r['count'], **extra)
+        # the other rules: the same float32 map on the slab in place - multiply, then add: two roundings
+        bc = (res.shape[0],) + (1,) * (res.dim() - 1)
+        res.mul_(torch.from_numpy(a.astype(np.float32)).to(res.device).reshape(bc))
+        res.add_(torch.from_numpy(b.astype(np.float32)).to(res.device).reshape(bc))
+        r = _coadd_combine(res, combine, sigma, maxiters, weights, frames, fscale, nlow, nhigh)
+        r.update(extra)
+        return r
+    return _coadd_combine(res, combine, sigma, maxiters, weights, frames, fscale, nlow, nhigh)
+
+
+def _coadd_combine(res, combine, sigma, maxiters, weights, frames, fscale, nlow, nhigh):
+    """The combine step of coadd on a resampled slab."""
     if combine == 'MEDIAN':
         med, cnt = stack_median(res, want_count=True)
         return dict(image=med, count=cnt)

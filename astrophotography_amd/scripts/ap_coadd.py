@@ -33,6 +33,14 @@ def command_line_opts(argv):
     parser.add_argument('--maxiters', default=5, type=int, metavar='N', help='CLIPPED and WINSORIZED; -1 = until convergence.')
     parser.add_argument('--nlow', default=1, type=int, metavar='N', help='MINMAX: lowest values dropped per pixel. Default: 1')
     parser.add_argument('--nhigh', default=1, type=int, metavar='N', help='MINMAX: highest values dropped per pixel. Default: 1')
+    parser.add_argument('--normalize', default='none', choices=['none', 'additive', 'multiplicative', 'additive+scaling'],
+                        help='Bring the resampled frames to the level of the reference frame before they are combined: by an offset '
+                             '(sky level), a factor (transparency) or scale and offset (noise and sky). Default: none')
+    parser.add_argument('--reference', default='0', metavar='FILE_OR_INDEX',
+                        help='The frame the others are normalised to: one of the input files or its index. Default: 0')
+    parser.add_argument('--weighting', default='none', choices=['none', 'noise'],
+                        help='WINSORIZED and MINMAX: average the surviving values with inverse-variance weights of the '
+                             'normalised frames. Default: none')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
     return parser.parse_args(argv)
 
@@ -60,7 +68,8 @@ def main(args=None):
         nx, ny = (int(v) for v in p.image_size.split(','))
         out_shape = (ny, nx)
     rs = ApResample(p.loglevel, combine=p.combine, sigma=p.sigma, maxiters=None if p.maxiters < 0 else p.maxiters,
-                    oversampling=p.oversampling, gain_keyword=p.gain_keyword, nlow=p.nlow, nhigh=p.nhigh)
+                    oversampling=p.oversampling, gain_keyword=p.gain_keyword, nlow=p.nlow, nhigh=p.nhigh, normalize=p.normalize, reference=p.reference,
+                    weighting=None if p.weighting == 'none' else p.weighting)
     center = None
     if p.center:
         center = tuple(float(v) for v in p.center.split(','))

@@ -144,7 +144,7 @@ typedef struct apgpu_stack_args {
     const float *bias;           /* [P] */
     const float *dark;           /* [P] */
     const float *nflat;          /* [P] or NULL */
-    const float *exp_ratio;      /* [N] */
+    const float *exp_ratio;      /* [N]; with APGPU_STACK_FRAME_PARAMS: [3][N] scale, offset, weight (below) */
     const float *pedestal;       /* [N] or NULL */
     int32_t dark_still_biased;
     int32_t center;              /* APGPU_CENTER_* */
@@ -219,6 +219,26 @@ typedef struct apgpu_stack_args {
 #define APGPU_STACK_REJECT_MINMAX 32
 #define APGPU_STACK_REJECT_MAX 128
 #define APGPU_STACK_WINSOR_MAX_INNER 16
+
+/* APGPU_STACK_FRAME_PARAMS: per-frame normalisation and weights inside the two rejection rules - frames of one night do not
+ * share a sky level or a scale, and a rule that compares the values of a pixel with each other needs them on one.  Valid only
+ * together with exactly one of APGPU_STACK_REJECT_WINSORIZED / APGPU_STACK_REJECT_MINMAX (without: APGPU_EUNSUPPORTED, the other
+ * stack kernels, apgpu_stack_median and apgpu_resample_stack_sigclip do not serve it).  With the bit:
+ *   bias, dark, nflat and pedestal must be NULL (APGPU_EINVAL): light frames are calibrated already, the fused calibration and
+ *   the frame parameters exclude each other;
+ *   exp_ratio must be non-NULL (APGPU_EINVAL) and points to float32 [3][n_frames] on the device: row 0 the scale a_i, row 1 the
+ *   offset b_i, row 2 the weight w_i.  The CALLER guarantees a_i and b_i finite and w_i finite and > 0 (the library cannot look);
+ *   pixmask, frame_stride, both dtypes, the outputs and APGPU_STACK_REJECT_MAX are as without the bit.
+ * Definition (no contraction: every multiply and add rounds):
+ *   x = the raw value as float32 (uint16 is exact);  v = float32(float32(a_i * x) + b_i)
+ *   S = the finite v of the column in frame order (a raw NaN or inf is not finite after the map either); the rule runs on S
+ *   exactly as defined above, the min/max tie rule by frame index included.
+ *   count = m; std_f64 = np.std(surv) as above - it is UNWEIGHTED; std = std_f64 rounded once.
+ *   mean_f64 = num / den, both sums over the survivors in frame order, sequentially from +0.0 in float64:
+ *       num += double(w_k) * double(v_k)       (the product of two widened float32 values is exact)
+ *       den += double(w_k)
+ *   which is np.cumsum(...)[-1] of the terms; mean = mean_f64 rounded once.  No survivor or a masked pixel: NaN and count 0. */
+#define APGPU_STACK_FRAME_PARAMS 64
 
 /* The two-kernel scheme and its workspace.  A clipped stack of up to 128 frames (and the chunked kernel for 129 .. 512) with
  * lean outputs runs as a FAST kernel - the float32 fast path alone, four wavefronts per SIMD - followed by a REDO PASS of the
