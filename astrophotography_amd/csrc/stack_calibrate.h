@@ -226,8 +226,11 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 // E_DIRECT (round 4; full stacks without pedestals): the exposure ratios are read straight from the caller's array `eg` - a
 // wave-uniform address with a constant offset, i.e. scalar loads into SGPR pairs that v_pk_mul_f32 takes as they are - instead
 // of from the LDS copy: no staging pass, no barrier before the first frame load, no ds_read in the calibration.
+// FINITE_LATER (round 7; the fast kernels): no `acc` chain - one v_pk_fma_f32 per frame pair whose only use is to learn whether a
+// calibrated value is NaN or +-inf.  The caller reads that off the column once it is sorted with NaN-propagating maxima
+// (sort_column's NANMAX, finite_ok_sorted); the return value is then nf_ok (and the range guard's, when RANGE_GUARD) alone.
 template <int NP, typename RawT, bool HAS_PED, int F0 = 0, int CNT = NP, bool RANGE_GUARD = true, int MINN = NP, bool UNI_E = false,
-          bool E_DIRECT = false>
+          bool E_DIRECT = false, bool FINITE_LATER = false>
 __device__ __forceinline__ bool calibrate_fast(const FrameScalars<NP> &fs, const RawT (&raw)[CNT], float b, float D, float nf,
                                                bool dodiv, float (&v)[NP], int nframes = NP, int plo = 0, const float *eg = nullptr)
 {
@@ -281,7 +284,7 @@ __device__ __forceinline__ bool calibrate_fast(const FrameScalars<NP> &fs, const
             const v2f q = __builtin_elementwise_fma(r0, y2, q0);
             v[f] = q.x;
             v[f + 1] = q.y;
-            acc = __builtin_elementwise_fma(q, zero2, acc);  // NaN iff some value is not finite
+            if constexpr (!FINITE_LATER) acc = __builtin_elementwise_fma(q, zero2, acc);  // NaN iff some value is not finite
             if constexpr (RANGE_GUARD) {
                 mx = fmaxf(fmaxf(mx, fabsf(q.x)), fabsf(q.y));
                 mn = fminf(fminf(mn, fabsf(q.x)), fabsf(q.y));
@@ -294,7 +297,8 @@ __device__ __forceinline__ bool calibrate_fast(const FrameScalars<NP> &fs, const
                     v[F0 + g] = (F0 + g < nframes + plo) ? -__builtin_inff() : __builtin_inff();   // the first plo pads sort to the bottom (split pads)
         }
         const bool range_ok = !RANGE_GUARD || !dodiv || (mx < 0x1p50f && mn > 0x1p-50f);
-        return nf_ok && range_ok && (acc.x == 0.f) && (acc.y == 0.f);
+        if constexpr (FINITE_LATER) return nf_ok && range_ok;
+        else return nf_ok && range_ok && (acc.x == 0.f) && (acc.y == 0.f);
     } else {
         float x = to_f32(raw[0]);
         if constexpr (HAS_PED) x = x + fs.ped[0];
@@ -325,7 +329,15 @@ __device__ __forceinline__ float uniform_pick(const float (&v)[NP], int idx)
 
 // nvalid (wave-uniform): the column's finite values occupy v[0 .. nvalid), +inf sentinels follow; MINN <= nvalid.
 // plo (wave-uniform, split pads): the column starts with plo -inf sentinels; the finite values occupy v[plo .. plo + nvalid).
-template <int NP, int MINN = NP>
+// FINITE (round 7): the column was calibrated WITHOUT the finite test (calibrate_fast's FINITE_LATER) and sorted with
+// NaN-propagating maxima (sort_column's NANMAX); the test then also says that every value is finite.
+//   NaN: any NaN of the column sits on v[NP - 1] (cmpx) - on the LAST SLOT, not on the last real value: it takes the place of
+//        the top +inf pad of a padded column.  (What the minima and medians made of a column that holds one does not matter.)
+//   +-inf: a NaN-free column is sorted, so an infinity is one of the real ends.
+// The ends meet in a NaN-propagating maximum - fmaxf(|lo|, |hi|) would swallow a NaN - and a lane that does not divide, which
+// has no quotient range to keep, is still tested against +inf.  (The slots a padded stack does not load - raw 0 in a partly real
+// group of eight - were in the `acc` chain and are not in this test: they never reach the sort.)
+template <int NP, int MINN = NP, bool FINITE = false>
 __device__ __forceinline__ bool range_ok_sorted(const float (&v)[NP], bool dodiv, int nvalid = NP, int plo = 0)
 {
     float lo = v[0];
@@ -335,7 +347,15 @@ __device__ __forceinline__ bool range_ok_sorted(const float (&v)[NP], bool dodiv
         if (plo > 0) lo = uniform_pick<0, NP>(v, plo);
         hi = uniform_pick<(MINN > 0 ? MINN - 1 : 0), NP>(v, plo + __builtin_amdgcn_readfirstlane(nvalid) - 1);
     }
-    const bool big_ok = fmaxf(fabsf(lo), fabsf(hi)) < 0x1p50f;
+    bool big_ok;
+    if constexpr (FINITE) {
+        float m;                                            // max(|lo|, |hi|), NaN if either is: one instruction for both ends
+        asm("v_maximum3_f32 %0, |%1|, |%2|, |%2|" : "=v"(m) : "v"(lo), "v"(hi));
+        big_ok = m < 0x1p50f || (!dodiv && m < __builtin_inff());   // (two compares against scalars + mask logic: no per-lane bound)
+        if constexpr (MINN < NP) big_ok = big_ok && (v[NP - 1] == v[NP - 1]);
+    } else {
+        big_ok = fmaxf(fabsf(lo), fabsf(hi)) < 0x1p50f;
+    }
     const bool one_sign = lo > 0x1p-50f || hi < -0x1p-50f;    // then min |q| = |lo| or |hi| and it is above 2^-50
     bool small_ok = one_sign;
     if (wave_any(dodiv && !one_sign)) {
@@ -348,7 +368,8 @@ __device__ __forceinline__ bool range_ok_sorted(const float (&v)[NP], bool dodiv
         }
         small_ok = mn > 0x1p-50f;
     }
-    return !dodiv || (big_ok && small_ok);
+    if constexpr (FINITE) return big_ok && (!dodiv || small_ok);
+    else return !dodiv || (big_ok && small_ok);
 }
 
 // A column's loads issued EARLY (round 4): the per-pixel masters first - the calibration's first instruction needs them, and
@@ -393,11 +414,13 @@ __device__ __forceinline__ bool ratios_uniform(const float *eg, int nframes)
 {
     typedef const float __attribute__((address_space(4))) cfloat;
     const cfloat *ec = (const cfloat *)(uintptr_t)eg;
+    // (bit patterns: a NaN ratio is "uniform" with itself - every column is then NaN either way - and -0.0 differs from +0.0,
+    // as it must: x - (+0) and x - (-0) differ for x = -0.  Differences are OR-ed, not tested one by one: no branch per frame.)
     const int e0 = __builtin_amdgcn_readfirstlane(__float_as_int(ec[0]));
-    bool same = true;
+    int diff = 0;
 #pragma unroll
-    for (int f = 1; f < NP; f++) same = same && (f >= nframes || __builtin_amdgcn_readfirstlane(__float_as_int(ec[f < nframes ? f : 0])) == e0);
-    return same;
+    for (int f = 1; f < NP; f++) diff |= __builtin_amdgcn_readfirstlane(__float_as_int(ec[f < nframes ? f : 0])) ^ e0;
+    return diff == 0;
 }
 
 // Per-lane context of a column load: what the exact fallback and the deferred range check need.

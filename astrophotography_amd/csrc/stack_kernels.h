@@ -586,68 +586,87 @@ __global__ __launch_bounds__(256, NP <= 64 ? APGPU_FAST_MIN_BLOCKS : ((FULL || P
             __builtin_amdgcn_sched_barrier(0);
             RawT half[HN];
             load_raw<NP, RawT, FULL, 0, HN, MINN, NS>(prm, base, lane, half);
-            good = calibrate_fast<NP, RawT, false, 0, HN, false, MINN, false, true>(fs, half, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
+            good = calibrate_fast<NP, RawT, false, 0, HN, false, MINN, false, true, true>(fs, half, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
             load_raw<NP, RawT, FULL, HN, HN, MINN, NS>(prm, base, lane, half);
-            good = calibrate_fast<NP, RawT, false, HN, HN, false, MINN, false, true>(fs, half, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
+            good = calibrate_fast<NP, RawT, false, HN, HN, false, MINN, false, true, true>(fs, half, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
         }
-        EarlyLoads<NP, RawT> L;
-        if constexpr (!HALVES) {
-            issue_early_loads<NP, RawT, CALIB, FULL, MINN, (PADS > 0 ? NP - PADS : 0)>(prm, base, lane, L);
-            good = !L.skip;
-        }
-        if constexpr (HALVES) {
-        } else if constexpr (CALIB) {
-            const float b = L.b;
-            const float D = prm.still_biased ? L.d - b : L.d;             // ApCalibrate.py:440-445
-            float nf = 1.f;
-            if (prm.nflat) {
-                nf = L.nf;
-                dodiv = (nf != 0.f);                        // ApCalibrate.py:462 (NaN != 0 is True)
+        // The rest of the tile, compiled once per form of the calibration and chosen per wave (round 7).  UNI: every frame has
+        // the exposure ratio of frame 0 (ratios_uniform: scalar loads and scalar arithmetic only) - the dark term e * D is formed
+        // once per pixel, one v_pk_mul_f32 less per frame pair.  The two forms share NOTHING after the test, the frame loads
+        // included: as two calibration bodies between one set of loads and one sort (rounds 4 and 5, and again with the registers
+        // the finite test gave back: 128 VGPRs + 22 .. 38 spilled, also with the whole tile behind the loads) the allocator
+        // cannot place v[]; as two complete copies each is the kernel it would be alone - 82 VGPRs, no scratch (64 slots).
+        // A wave executes one of them.  (The half-column kernels, 104 .. 128 slots, keep the per-frame form alone.)
+        auto rest = [&](auto uni_c) {
+            constexpr bool UNI = decltype(uni_c)::value;
+            EarlyLoads<NP, RawT> L;
+            if constexpr (!HALVES) {
+                issue_early_loads<NP, RawT, CALIB, FULL, MINN, (PADS > 0 ? NP - PADS : 0)>(prm, base, lane, L);
+                good = !L.skip;
             }
-            // (measured again on this kernel: a second calibration body for "one exposure ratio", e * D formed once per pixel,
-            // -32 instructions - the two bodies' v[] meet in one register set: 128 VGPRs + 36 spilled; not built)
-            good = calibrate_fast<NP, RawT, false, 0, NP, false, MINN, false, true>(fs, L.raw, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
-        } else {
-            // non-finite values (astropy masks them) become +inf sentinels; padding slots: the first plo -inf, the others +inf
+            if constexpr (HALVES) {
+            } else if constexpr (CALIB) {
+                const float b = L.b;
+                const float D = prm.still_biased ? L.d - b : L.d;         // ApCalibrate.py:440-445
+                float nf = 1.f;
+                if (prm.nflat) {
+                    nf = L.nf;
+                    dodiv = (nf != 0.f);                    // ApCalibrate.py:462 (NaN != 0 is True)
+                }
+                good = calibrate_fast<NP, RawT, false, 0, NP, false, MINN, UNI, true, true>(fs, L.raw, b, D, nf, dodiv, v, N, plo, prm.exp_ratio) && good;
+            } else {
+                // non-finite values (astropy masks them) become +inf sentinels; padding slots: the first plo -inf, the others +inf
 #pragma unroll
-            for (int f = 0; f < NP; f++) {
-                if (FULL || f < MINN || f < N) {
-                    const float x = L.raw[f];
-                    v[f] = fabsf(x) < __builtin_inff() ? x : __builtin_inff();
-                } else {
-                    v[f] = (f < N + plo) ? -__builtin_inff() : __builtin_inff();
+                for (int f = 0; f < NP; f++) {
+                    if (FULL || f < MINN || f < N) {
+                        const float x = L.raw[f];
+                        v[f] = fabsf(x) < __builtin_inff() ? x : __builtin_inff();
+                    } else {
+                        v[f] = (f < N + plo) ? -__builtin_inff() : __builtin_inff();
+                    }
                 }
             }
+#ifdef APGPU_VARIANT_STRIP
+            // measurement only (tools/variant_lib.sh): THIS kernel without its clip - 2: loads + calibration, the column summed; 1: the
+            // pruned sort and the range test as well, then the column summed - the floor rows of DESIGN 4.1 (round 5: measured on the
+            // kernel that ships, same control flow up to the cut, same residency: the LDS block below holds it at four workgroups per CU)
+            if (wave_any(good)) {
+                if (APGPU_VARIANT_STRIP == 1) {
+                    sort_column<NP, T, CALIB>(v);
+                    if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN, true>(v, dodiv, N, plo);
+                }
+                float acc[4] = {good ? 0.f : 1.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < NP; i++) acc[i & 3] += v[i];
+                if (prm.mean) prm.mean[p] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            }
+            return;
+#endif
+            if (wave_any(good)) {
+                // (calibrated columns: no finite test so far - calibrate_fast's FINITE_LATER; the sort carries a NaN to the last
+                // slot and range_ok_sorted reads it, and an infinity, off the ends)
+                sort_column<NP, T, CALIB>(v);
+                if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN, true>(v, dodiv, N, plo);
+                else {
+                    // the sentinels sit at the top: count them in the upper tail (pads included); a full tail = too many
+#pragma unroll
+                    for (int k = 1; k <= T; k++) nonfin += (v[NP - k] == __builtin_inff()) ? 1 : 0;
+                    good = good && nonfin < T;
+                }
+                if (wave_any(good)) finish_fast_column<NP, T, CALIB, PLO, PHI, PLUS>(v, good, p, plo, CALIB ? phi : nonfin);
+            }
+        };
+        if constexpr (CALIB && !HALVES) {
+            if (ratios_uniform<NP>(prm.exp_ratio, N)) rest(std::true_type{});
+            else rest(std::false_type{});
+        } else {
+            rest(std::false_type{});
         }
 #ifdef APGPU_VARIANT_STRIP
-        // measurement only (tools/variant_lib.sh): THIS kernel without its clip - 2: loads + calibration, the column summed; 1: the
-        // pruned sort and the range test as well, then the column summed - the floor rows of DESIGN 4.1 (round 5: measured on the
-        // kernel that ships, same control flow up to the cut, same residency: the LDS block below holds it at four workgroups per CU)
-        if (wave_any(good)) {
-            if (APGPU_VARIANT_STRIP == 1) {
-                sort_column<NP, T>(v);
-                if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN>(v, dodiv, N, plo);
-            }
-            float acc[4] = {good ? 0.f : 1.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < NP; i++) acc[i & 3] += v[i];
-            if (prm.mean) prm.mean[p] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-        }
         __shared__ char geometry[40 * 1024];
         if (prm.N < 0) geometry[lane] = 1;
         return;
 #endif
-        if (wave_any(good)) {
-            sort_column<NP, T>(v);
-            if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN>(v, dodiv, N, plo);
-            else {
-                // the sentinels sit at the top: count them in the upper tail (pads included); a full tail = too many
-#pragma unroll
-                for (int k = 1; k <= T; k++) nonfin += (v[NP - k] == __builtin_inff()) ? 1 : 0;
-                good = good && nonfin < T;
-            }
-            if (wave_any(good)) finish_fast_column<NP, T, CALIB, PLO, PHI, PLUS>(v, good, p, plo, CALIB ? phi : nonfin);
-        }
     }
     // (finished blocks are counted BEFORE their pixels are listed: whoever reads the line in between underestimates the rate)
     fast_blocks_done<256>(alert, prm.redo);
@@ -821,7 +840,10 @@ __device__ __forceinline__ bool fast_raw_column(const FrameScalars<NP> &fs, cons
         if constexpr (CALIB) {
             // non-decreasing map (finite masters, a positive or unused flat): the calibrated column is sorted like the raw one
             const bool increasing = (fabsf(b) < __builtin_inff()) && (fabsf(D) < __builtin_inff()) && (!dv || (nf > 0.f && nf < __builtin_inff()));
-            good = calibrate_fast<NP, float, false, 0, NP, false, NP, true, true>(fs, rawf, b, D, nf, dv, v, NP, 0, eg) && increasing && good;
+            // (no finite test per value, FINITE_LATER: the raw column is sorted and the map monotone, so the calibrated column is
+            // sorted - no second sort has to carry a NaN anywhere - and the first value the map overflows on, or all of them
+            // when a master or the ratio is not finite, is an end of it: range_ok_sorted's end test below sees it)
+            good = calibrate_fast<NP, float, false, 0, NP, false, NP, true, true, true>(fs, rawf, b, D, nf, dv, v, NP, 0, eg) && increasing && good;
         } else {
 #pragma unroll
             for (int f = 0; f < NP; f++) v[f] = rawf[f];
@@ -834,7 +856,7 @@ __device__ __forceinline__ bool fast_raw_column(const FrameScalars<NP> &fs, cons
             if (i >= MINN && i >= NP - phi) v[i] = __builtin_inff();
         }
     }
-    if constexpr (CALIB) good = good && range_ok_sorted<NP, (MINN < NP ? MINN : 0)>(v, dv, N, plo);
+    if constexpr (CALIB) good = good && range_ok_sorted<NP, (MINN < NP ? MINN : 0), true>(v, dv, N, plo);
     if (wave_any(good)) finish_fast_column<NP, T, true, PLO, PHI>(v, good, p, plo, phi);
     return good;
 }

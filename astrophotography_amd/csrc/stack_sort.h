@@ -122,11 +122,46 @@ constexpr Net<NP> make_window_net()
 // Compare-exchange.  Written as the two machine instructions: through fminf/fmaxf the compiler has to
 // quiet possible signalling NaNs first (IEEE mode) and adds a v_max_f32 x, x, x canonicalisation per
 // network input (~120 instructions per column); the columns are NaN-free by construction here.
+//
+// NANMAX (off by default; the fast kernels' calibrated columns turn it on, stack_kernels.h): every MAXIMUM of cmpx / sort3 /
+// sort4 is emitted as v_maximum3_f32, which returns NaN when an input is NaN (the two-input form repeats an operand); it is of
+// the same 4-cycle class as v_max_f32 and orders +0 above -0 like it, so a NaN-free column sorts bit for bit as before.  Minima
+// and v_med3_f32 stay as they are.  Then a NaN ANYWHERE in the column ends on the network's last wire: in a network whose last
+// output is the true maximum, the largest input reaches that output through maximum outputs only - which wire it leaves a
+// sorter on depends on the wires alone, not on the other values - and on that same path every sorter hands the NaN on to its
+// top wire, whatever its other outputs make of it.  (The pruned networks keep that path: their last output is always needed.)
+// So "no value is NaN" is one test of v[NP - 1] after the sort instead of one operation per value before it.
+__device__ __forceinline__ float max2(float x, float y, std::false_type)
+{
+    float hi;
+    asm("v_max_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
+    return hi;
+}
+__device__ __forceinline__ float max2(float x, float y, std::true_type)
+{
+    float hi;
+    asm("v_maximum3_f32 %0, %1, %2, %2" : "=v"(hi) : "v"(x), "v"(y));
+    return hi;
+}
+__device__ __forceinline__ float max3(float x, float y, float z, std::false_type)
+{
+    float hi;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(hi) : "v"(x), "v"(y), "v"(z));
+    return hi;
+}
+__device__ __forceinline__ float max3(float x, float y, float z, std::true_type)
+{
+    float hi;
+    asm("v_maximum3_f32 %0, %1, %2, %3" : "=v"(hi) : "v"(x), "v"(y), "v"(z));
+    return hi;
+}
+
+template <bool NANMAX = false>
 __device__ __forceinline__ void cmpx(float &x, float &y)
 {
-    float lo, hi;
+    float lo;
     asm("v_min_f32 %0, %1, %2" : "=v"(lo) : "v"(x), "v"(y));
-    asm("v_max_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
+    const float hi = max2(x, y, std::bool_constant<NANMAX>{});
     x = lo;
     y = hi;
 }
@@ -134,38 +169,39 @@ __device__ __forceinline__ void cmpx(float &x, float &y)
 // Four values sorted with the three-input instructions: min3 / med3 / max3 sort three (one instruction per output where a
 // compare-exchange network needs two per pair), and the fourth is inserted with min, med3, med3, max - 7 instructions
 // instead of the 10 of the 5-comparator network (all of the same 4-cycle class, tools/issue_cost.hip).
+template <bool NANMAX = false>
 __device__ __forceinline__ void sort4(float &a, float &b, float &c, float &d)
 {
-    float x0, x1, x2, o0, o1, o2, o3;
+    float x0, x1, o0, o1, o2;
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(x0) : "v"(a), "v"(b), "v"(c));
     asm("v_med3_f32 %0, %1, %2, %3" : "=v"(x1) : "v"(a), "v"(b), "v"(c));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(x2) : "v"(a), "v"(b), "v"(c));
+    const float x2 = max3(a, b, c, std::bool_constant<NANMAX>{});
     asm("v_min_f32 %0, %1, %2" : "=v"(o0) : "v"(x0), "v"(d));
     asm("v_med3_f32 %0, %1, %2, %3" : "=v"(o1) : "v"(x0), "v"(x1), "v"(d));
     asm("v_med3_f32 %0, %1, %2, %3" : "=v"(o2) : "v"(x1), "v"(x2), "v"(d));
-    asm("v_max_f32 %0, %1, %2" : "=v"(o3) : "v"(x2), "v"(d));
+    const float o3 = max2(x2, d, std::bool_constant<NANMAX>{});
     a = o0;
     b = o1;
     c = o2;
     d = o3;
 }
 
-template <int NP, int P0, int T, int BASE, int... I>
+template <int NP, int P0, int T, int BASE, bool NANMAX, int... I>
 __device__ __forceinline__ void net_chunk(float (&v)[NP], std::integer_sequence<int, I...>)
 {
     constexpr Net<NP> net = T > 0 ? make_pruned_net<NP, P0, (T > 0 ? T : 1)>() : make_net<NP, P0>();
-    (cmpx(v[net.ce[BASE + I].a], v[net.ce[BASE + I].b]), ...);
+    (cmpx<NANMAX>(v[net.ce[BASE + I].a], v[net.ce[BASE + I].b]), ...);
 }
 
-template <int NP, int P0, int T, int BASE>
+template <int NP, int P0, int T, int BASE, bool NANMAX = false>
 __device__ __forceinline__ void net_from(float (&v)[NP])
 {
     constexpr int total = T > 0 ? make_pruned_net<NP, P0, (T > 0 ? T : 1)>().n : make_net<NP, P0>().n;
     constexpr int CH = 64;
     if constexpr (BASE < total) {
         constexpr int len = (total - BASE < CH) ? total - BASE : CH;
-        net_chunk<NP, P0, T, BASE>(v, std::make_integer_sequence<int, len>{});
-        net_from<NP, P0, T, BASE + len>(v);
+        net_chunk<NP, P0, T, BASE, NANMAX>(v, std::make_integer_sequence<int, len>{});
+        net_from<NP, P0, T, BASE + len, NANMAX>(v);
     }
 }
 
@@ -298,59 +334,61 @@ constexpr OpNet<NP> make_opnet()
 template <int NP, int T>
 inline constexpr OpNet<NP> kOpNet = make_opnet<NP, T>();
 
+template <bool NANMAX = false>
 __device__ __forceinline__ void sort3(float &a, float &b, float &c)
 {
-    float x0, x1, x2;
+    float x0, x1;
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(x0) : "v"(a), "v"(b), "v"(c));
     asm("v_med3_f32 %0, %1, %2, %3" : "=v"(x1) : "v"(a), "v"(b), "v"(c));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(x2) : "v"(a), "v"(b), "v"(c));
+    const float x2 = max3(a, b, c, std::bool_constant<NANMAX>{});
     a = x0;
     b = x1;
     c = x2;
 }
 
-template <int NP, int T, int I>
+template <int NP, int T, int I, bool NANMAX>
 __device__ __forceinline__ void opnet_apply(float (&v)[NP])
 {
     constexpr NetOp o = kOpNet<NP, T>.op[I];
-    if constexpr (o.k == 2) cmpx(v[o.w[0]], v[o.w[1]]);
-    else if constexpr (o.k == 3) sort3(v[o.w[0]], v[o.w[1]], v[o.w[2]]);
-    else sort4(v[o.w[0]], v[o.w[1]], v[o.w[2]], v[o.w[3]]);
+    if constexpr (o.k == 2) cmpx<NANMAX>(v[o.w[0]], v[o.w[1]]);
+    else if constexpr (o.k == 3) sort3<NANMAX>(v[o.w[0]], v[o.w[1]], v[o.w[2]]);
+    else sort4<NANMAX>(v[o.w[0]], v[o.w[1]], v[o.w[2]], v[o.w[3]]);
 }
 
-template <int NP, int T, int BASE, int... I>
+template <int NP, int T, int BASE, bool NANMAX, int... I>
 __device__ __forceinline__ void opnet_chunk(float (&v)[NP], std::integer_sequence<int, I...>)
 {
-    (opnet_apply<NP, T, BASE + I>(v), ...);
+    (opnet_apply<NP, T, BASE + I, NANMAX>(v), ...);
 }
 
-template <int NP, int T, int BASE = 0>
+template <int NP, int T, int BASE = 0, bool NANMAX = false>
 __device__ __forceinline__ void opnet_from(float (&v)[NP])
 {
     constexpr int total = kOpNet<NP, T>.n;
     constexpr int CH = 64;
     if constexpr (BASE < total) {
         constexpr int len = (total - BASE < CH) ? total - BASE : CH;
-        opnet_chunk<NP, T, BASE>(v, std::make_integer_sequence<int, len>{});
-        opnet_from<NP, T, BASE + len>(v);
+        opnet_chunk<NP, T, BASE, NANMAX>(v, std::make_integer_sequence<int, len>{});
+        opnet_from<NP, T, BASE + len, NANMAX>(v);
     }
 }
 
 // PRUNE_T > 0: only the outputs clip_fast32 reads come out sorted (make_pruned_net / make_opnet).
-template <int NP, int PRUNE_T = 0>
+// NANMAX: NaN-propagating maxima - a NaN in the column comes out on v[NP - 1] (see cmpx).
+template <int NP, int PRUNE_T = 0, bool NANMAX = false>
 __device__ __forceinline__ void sort_column(float (&v)[NP])
 {
 #ifndef APGPU_VARIANT_BATCHER_ONLY
     if constexpr (NP >= 8 && NP % 4 == 0) {
-        opnet_from<NP, PRUNE_T>(v);
+        opnet_from<NP, PRUNE_T, 0, NANMAX>(v);
     } else
 #endif
     if constexpr (NP >= 4 && NP % 4 == 0) {
 #pragma unroll
-        for (int g = 0; g < NP; g += 4) sort4(v[g], v[g + 1], v[g + 2], v[g + 3]);
-        net_from<NP, 4, PRUNE_T, 0>(v);
+        for (int g = 0; g < NP; g += 4) sort4<NANMAX>(v[g], v[g + 1], v[g + 2], v[g + 3]);
+        net_from<NP, 4, PRUNE_T, 0, NANMAX>(v);
     } else if constexpr (NP > 1) {
-        net_from<NP, 1, PRUNE_T, 0>(v);
+        net_from<NP, 1, PRUNE_T, 0, NANMAX>(v);
     }
 }
 
