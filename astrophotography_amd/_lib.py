@@ -17,7 +17,8 @@ MAX_STACK = 512
 STACK_EXACT_MOMENTS, STACK_MOMENTS_MEAN, STACK_SINGLE_KERNEL, STACK_NONFINITE_UNCLIPPED = 1, 2, 4, 8    # apgpu_stack_args.flags
 STACK_REJECT_WINSORIZED, STACK_REJECT_MINMAX = 16, 32   # apgpu_stack_args.flags: the rejection rules of small stacks (ops.stack_reject)
 STACK_FRAME_PARAMS = 64                                 # APGPU_STACK_FRAME_PARAMS: exp_ratio = float32 [3][N] scale, offset, weight (with a rejection rule)
-STACK_REJECT_MAX = 128                                  # APGPU_STACK_REJECT_MAX: frames a rejection rule takes
+STACK_FRAME_LOCAL = 128                                 # APGPU_STACK_FRAME_LOCAL: workspace = a host StackLocal (scale / offset meshes; with a rejection rule)
+STACK_REJECT_MAX = 128                                # APGPU_STACK_REJECT_MAX: frames a rejection rule takes
 CCDPROC_FORM = {'astropy': 0, 'legacy': 1}                                  # APGPU_CCDPROC_*
 STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_OFFSET: int64 calls, pixels, pixels listed, 64-pixel blocks given up
 
@@ -53,6 +54,14 @@ class StackArgs(C.Structure):
         ('count', C.c_void_p), ('moments', C.c_void_p), ('frame_stride', C.c_int64),
         ('mean_f64', C.c_void_p), ('std_f64', C.c_void_p), ('moments_f64', C.c_int32), ('flags', C.c_int32),
         ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+    ]
+
+
+class StackLocal(C.Structure):
+    """struct apgpu_stack_local (include/apgpu.h): the descriptor APGPU_STACK_FRAME_LOCAL finds in StackArgs.workspace."""
+    _fields_ = [
+        ('width', C.c_int64), ('row0', C.c_int64), ('box_height', C.c_int32), ('box_width', C.c_int32),
+        ('ny', C.c_int32), ('nx', C.c_int32), ('scale', C.c_void_p), ('offset', C.c_void_p), ('weight', C.c_void_p),
     ]
 
 

@@ -23,7 +23,7 @@ NORMALIZE_MODES = ('none', 'additive', 'multiplicative', 'additive+scaling')
 
 class ApResample:
     def __init__(self, loglevel='INFO', combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024, conserve_flux=True, oversampling=1,
-                 gain_keyword='EGAIN', nlow=1, nhigh=1, normalize='none', reference=0, weighting=None):
+                 gain_keyword='EGAIN', nlow=1, nhigh=1, normalize='none', reference=0, weighting=None, norm_box=None):
         self._name = 'ApResample'
         self._logger = _common.make_logger(self._name, loglevel)
         combine = str(combine).upper()
@@ -47,18 +47,27 @@ class ApResample:
             raise ValueError(f'Error, weighting {weighting} goes with combine WINSORIZED and MINMAX only, not {combine}.')
         self.normalize, self.weighting = normalize, weighting
         self.reference = reference                          # a frame index, or (coadd_files) a file name
+        # the LOCAL normalisation: statistics per norm_box x norm_box box, scale and offset interpolated per pixel (ops.local_normalization)
+        if norm_box is not None:
+            if isinstance(norm_box, bool) or int(norm_box) != norm_box or not 1 <= int(norm_box) <= 32768:
+                raise ValueError(f'Error, norm_box {norm_box} is not a whole number of pixels in 1..32768')
+            if combine not in ('WINSORIZED', 'MINMAX'):
+                raise ValueError(f'Error, norm_box goes with combine WINSORIZED and MINMAX only, not {combine}.')
+            norm_box = int(norm_box)
+        self.norm_box = norm_box
 
     def coadd(self, frames, affines, fscale=None, mask=None, out_shape=None, weights=None, fine_affines=None, fused=False, reference=None):
         """frames [N,H,W] float32 device tensor -> dict(image, count[, weight]) device tensors.  fused: ops.coadd's one-launch
         form (CLIPPED / AVERAGE of up to 16 frames, no resampled slab in memory).  With a normalisation the result also holds
-        scale, offset and norm_weights per frame; reference: the frame index (default: the constructor's)."""
+        scale, offset and norm_weights per frame (with norm_box: scale and offset meshes [N, ny, nx], and norm_box); reference: the frame index (default: the constructor's)."""
         from .. import ops
-        if self.normalize != 'none' or self.weighting is not None:
+        if self.normalize != 'none' or self.weighting is not None or self.norm_box is not None:
+            kw = {} if self.norm_box is None else dict(norm_box=self.norm_box)
             ref = self.reference if reference is None else reference
             return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                              sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
                              oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
-                             nlow=self.nlow, nhigh=self.nhigh, normalize=self.normalize, reference=int(ref), weighting=self.weighting)
+                             nlow=self.nlow, nhigh=self.nhigh, normalize=self.normalize, reference=int(ref), weighting=self.weighting, **kw)
         return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                          sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
                          oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
@@ -185,10 +194,14 @@ class ApResample:
             hdr['NORMMODE'] = (self.normalize, 'Frame normalisation before the combine')
             hdr['NORMREF'] = (Path(input_files[ref]).name, 'Reference frame of the normalisation')
             hdr['NORMWGT'] = (self.weighting or 'none', 'Weighting of the surviving values')
+            local = 'norm_box' in res                        # meshes: the keywords hold each frame's median
+            if local:
+                hdr['NORMBOX'] = (int(res['norm_box'][0]), 'Box of the local normalisation (pixels)')
             for idx, fname in enumerate(input_files):
-                a, b, w = float(res['scale'][idx]), float(res['offset'][idx]), float(res['norm_weights'][idx])
-                hdr[f'NSCL{idx:03d}'] = (a, 'Normalisation scale of IFILE%03d' % idx)
-                hdr[f'NOFF{idx:03d}'] = (b, 'Normalisation offset of IFILE%03d' % idx)
+                a = 1.0 if res['scale'] is None else float(np.median(res['scale'][idx]))
+                b, w = float(np.median(res['offset'][idx])), float(res['norm_weights'][idx])
+                hdr[f'NSCL{idx:03d}'] = (a, ('Median normalisation scale of IFILE%03d' if local else 'Normalisation scale of IFILE%03d') % idx)
+                hdr[f'NOFF{idx:03d}'] = (b, ('Median normalisation offset of IFILE%03d' if local else 'Normalisation offset of IFILE%03d') % idx)
                 hdr[f'NWGT{idx:03d}'] = (w, 'Weight of IFILE%03d' % idx)
                 self._logger.info(f'  File {Path(fname).name:40s} NSCALE {a:10.6f} NOFFSET {b:12.6g} NWEIGHT {w:8.6f}')
         hdr['RESAMPT'] = ('LANCZOS3', 'Resampling kernel')

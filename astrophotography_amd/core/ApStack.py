@@ -42,7 +42,7 @@ class ApStack:
         self.nlow, self.nhigh = nlow, nhigh
 
     def stack(self, frames, method='sigclip', calib=None, pixmask=None, outputs=('mean',), normalize='none', reference=0,
-              weighting=None):
+              weighting=None, norm_box=None):
         """frames[N,H,W] device tensor (uint16|float32) -> dict of device tensors.
 
         method 'sigclip': clipped mean (+ 'median', 'std', 'count', 'moments' planes on request);
@@ -53,6 +53,10 @@ class ApStack:
         'additive+scaling': the frames brought to frame `reference`'s level inside the kernel, ops.frame_stats /
         ops.frame_normalization) and weighting='noise' (the survivors averaged with inverse-variance weights) on a slab that is
         not calibrated in the same call; the result then also holds scale, offset and norm_weights (float64 numpy [N]).
+        norm_box (an int or (bh, bw); those two methods only): the LOCAL normalisation - the statistics are taken per box
+        (ops.local_stats), scale and offset are meshes interpolated at every pixel inside the kernel (ops.local_normalization)
+        - for frames whose sky differs in shape; scale (None without a scaling mode) and offset are then float32 numpy
+        [N, ny, nx] and the result also holds norm_box.
         calib: None or ApCalibrate.masters() + exp_ratio (+ pedestal) for the fused path."""
         from .. import ops
         from .._lib import MAX_STACK, STACK_REJECT_MAX
@@ -61,6 +65,21 @@ class ApStack:
         normed = normalize not in (None, 'none') or weighting not in (None, 'none')
         if normed and method not in REJECT_METHODS:
             raise ValueError(f'Error, normalize / weighting go with the methods {REJECT_METHODS}, not {method}.')
+        if norm_box is not None:
+            if method not in REJECT_METHODS:
+                raise ValueError(f'Error, norm_box (the local normalisation) goes with the methods {REJECT_METHODS}, not {method} '
+                                 '(minmax with nlow = nhigh = 0 is the normalised, weighted average).')
+            if calib is not None:
+                raise ValueError('Error, norm_box needs calibrated frames: it does not go with the fused calibration.')
+            if frames.shape[0] > STACK_REJECT_MAX:
+                raise ValueError(f'Error, stacking method {method} takes at most {STACK_REJECT_MAX} frames, got {frames.shape[0]}.')
+            a, b, w = ops.local_normalization(ops.local_stats(frames, norm_box), normalize or 'none', reference=reference,
+                                              weighting=None if weighting in (None, 'none') else weighting, box=norm_box)
+            res = ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
+                                   maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, pixmask=pixmask, outputs=outputs,
+                                   scale=a, offset=b, weights=w, box=norm_box)
+            res.update(scale=a, offset=b, norm_weights=w, norm_box=ops._box_pair(norm_box))
+            return res
         if method in REJECT_METHODS:
             if frames.shape[0] > STACK_REJECT_MAX:
                 raise ValueError(f'Error, stacking method {method} takes at most {STACK_REJECT_MAX} frames, got {frames.shape[0]}.')

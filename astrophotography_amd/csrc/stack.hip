@@ -86,11 +86,37 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
     if ((args->flags & APGPU_STACK_FRAME_PARAMS) && (median_only || !(args->flags & kReject)))
         return fail(APGPU_EUNSUPPORTED, "stack: APGPU_STACK_FRAME_PARAMS is served by the rejection rules only (APGPU_STACK_REJECT_WINSORIZED "
                     "or APGPU_STACK_REJECT_MINMAX of apgpu_stack_sigclip)");
+    if ((args->flags & APGPU_STACK_FRAME_LOCAL) && (median_only || !(args->flags & kReject)))
+        return fail(APGPU_EUNSUPPORTED, "stack: APGPU_STACK_FRAME_LOCAL is served by the rejection rules only (APGPU_STACK_REJECT_WINSORIZED "
+                    "or APGPU_STACK_REJECT_MINMAX of apgpu_stack_sigclip)");
     if (!median_only && (args->flags & kReject)) {
         // Winsorized clipping / min-max rejection (stack_reject.hip): one launch, no workspace - `workspace` is not looked at
+        // (with APGPU_STACK_FRAME_LOCAL it is the descriptor of the meshes, on the host)
         constexpr int kNoEffect = APGPU_STACK_EXACT_MOMENTS | APGPU_STACK_MOMENTS_MEAN | APGPU_STACK_SINGLE_KERNEL;
-        if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED | APGPU_STACK_FRAME_PARAMS))
+        if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED | APGPU_STACK_FRAME_PARAMS | APGPU_STACK_FRAME_LOCAL))
             return fail(APGPU_EINVAL, "stack: unknown flags 0x%x", args->flags);
+        if (args->flags & APGPU_STACK_FRAME_LOCAL) {
+            if (args->flags & APGPU_STACK_FRAME_PARAMS)
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL and APGPU_STACK_FRAME_PARAMS exclude each other");
+            if (args->bias || args->dark || args->nflat || args->pedestal || args->exp_ratio)
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL excludes the fused calibration and the frame parameters (bias, dark, "
+                            "nflat, pedestal and exp_ratio must be NULL)");
+            if (!args->workspace || args->workspace_bytes != sizeof(apgpu_stack_local))
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL needs workspace = a host apgpu_stack_local and workspace_bytes = %zu",
+                            sizeof(apgpu_stack_local));
+            const apgpu_stack_local *loc = static_cast<const apgpu_stack_local *>(args->workspace);
+            constexpr int64_t kMaxSide = 0x3fffffff;
+            if (loc->width < 1 || loc->width > kMaxSide || args->n_pixels % loc->width != 0)
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_local.width = %lld must be 1 .. 2^30 - 1 and divide n_pixels = %lld",
+                            (long long)loc->width, (long long)args->n_pixels);
+            if (loc->row0 < 0 || loc->row0 > kMaxSide || loc->row0 + args->n_pixels / loc->width > kMaxSide)
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_local.row0 = %lld (image rows are limited to 2^30)", (long long)loc->row0);
+            if (loc->box_height < 1 || loc->box_height > 32768 || loc->box_width < 1 || loc->box_width > 32768)
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_local box %d x %d (1 .. 32768)", loc->box_height, loc->box_width);
+            if (loc->ny < 1 || loc->nx < 1 || (int64_t)loc->ny * loc->nx > 0x7fffffff)
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_local mesh %d x %d", loc->ny, loc->nx);
+            if (!loc->offset) return fail(APGPU_EINVAL, "stack: apgpu_stack_local.offset is NULL");
+        }
         if (args->flags & APGPU_STACK_FRAME_PARAMS) {
             // exp_ratio is float32 [3][n_frames]: scale, offset, weight of every frame; light frames are calibrated already
             if (args->bias || args->dark || args->nflat || args->pedestal)

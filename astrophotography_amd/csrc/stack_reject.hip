@@ -22,6 +22,8 @@
 //   APGPU_STACK_FRAME_PARAMS (exp_ratio = float32 [3][N]: scale a, offset b, weight w; no calibration): the column is
 //   v = float32(float32(a_i x) + b_i), the rule runs on the finite v, count and std_f64 as above (unweighted), and
 //   mean_f64 = num / den, num += double(w_k) double(v_k), den += double(w_k) over the survivors in frame order from +0.0.
+//   APGPU_STACK_FRAME_LOCAL (workspace = a host apgpu_stack_local; no calibration, no exp_ratio): a and b are per-frame MESHES, one
+//   value per box, read off bilinearly at the pixel (mesh_axis, mesh_value, local_map below); everything behind v is as above.
 //
 // THE KERNEL.  One pixel per lane, one wavefront per workgroup, the column v[NP] in VGPRs IN FRAME ORDER and COMPACT: v[0 .. n)
 // are the lane's current S, v[n .. NP) are NaN.  numpy's sum of n <= 128 terms puts term i into accumulator i % 8 (i < n - n % 8)
@@ -54,6 +56,10 @@ struct RejectParams {
     double kl, kh;          // Winsorized: sigma_lower, sigma_upper
     int N, still_biased, maxiters;
     int minmax, nlow, nhigh;
+    // APGPU_STACK_FRAME_LOCAL (behind everything older: the other instances' arguments keep their places)
+    const float *lscale, *loffset, *lweight;                // meshes [N][ny][nx] (lscale may be NULL = 1), weights [N] or NULL = 1
+    int64_t width, row0;                                     // pixel p is image row row0 + p / width, column p % width
+    int bh, bw, ny, nx;                                      // box size, mesh shape
 };
 
 constexpr int kWinsorMaxInner = APGPU_STACK_WINSOR_MAX_INNER;
@@ -215,12 +221,55 @@ __device__ __forceinline__ double np_pass(const float (&v)[NP], int n, int nmin8
 // v = float32(float32(a x) + b): the map of APGPU_STACK_FRAME_PARAMS, each operation rounded on its own
 __device__ __forceinline__ float frame_map(float x, float a, float b) { return __fadd_rn(__fmul_rn(a, x), b); }
 
+// APGPU_STACK_FRAME_LOCAL: where a pixel coordinate c lies between the box centres (j + 0.5) b - 0.5 of a mesh axis of m cells:
+// the lower cell j0, the upper one j1 (the same cell beyond the outer centres and on a one-cell axis) and the fraction t.  Whole
+// numbers throughout (c < 2^30, b <= 32768: stack_dispatch has seen to it), one IEEE division of two exactly held values.
+__device__ __forceinline__ void mesh_axis(int c, int b, int m, int &j0, int &j1, float &t)
+{
+    const int u = 2 * c + 1 - b, b2 = 2 * b;                 // u > -2 b: floor(u / 2b) is -1 for a negative u, clamped to 0
+    const int top = m >= 2 ? m - 2 : 0;
+    const int q = u < 0 ? 0 : u / b2;
+    j0 = q < top ? q : top;
+    j1 = j0 + 1 < m ? j0 + 1 : m - 1;
+    int r = u - b2 * j0;
+    r = r < 0 ? 0 : (r > b2 ? b2 : r);
+    t = __fdiv_rn((float)r, (float)b2);
+}
+
+// a lane's place in the meshes: the four corners' indices inside a frame's [ny][nx] mesh and the two fractions
+struct MeshCell {
+    int i00, i01, i10, i11;
+    float tx, ty;
+};
+
+// m(y, x) = top + ty (bot - top), top = M[j0][k0] + tx (M[j0][k1] - M[j0][k0]), bot the same on row j1: every operation rounds
+__device__ __forceinline__ float mesh_value(const float *M, const MeshCell &c)
+{
+    const float m00 = M[c.i00], m01 = M[c.i01], m10 = M[c.i10], m11 = M[c.i11];
+    const float top = __fadd_rn(m00, __fmul_rn(c.tx, __fsub_rn(m01, m00)));
+    const float bot = __fadd_rn(m10, __fmul_rn(c.tx, __fsub_rn(m11, m10)));
+    return __fadd_rn(top, __fmul_rn(c.ty, __fsub_rn(bot, top)));
+}
+
+// v = float32(float32(a(y,x) x) + b(y,x)) of frame f; without a scale mesh v = float32(x + b), the bits a mesh of ones gives.
+// The one place the local map is formed: the first load and the weighted walk both come through here.
+__device__ __forceinline__ float local_map(float x, const float *lscale, const float *loffset, int64_t cells, int f, const MeshCell &c)
+{
+    const float b = mesh_value(loffset + f * cells, c);
+    if (lscale) x = __fmul_rn(mesh_value(lscale + f * cells, c), x);      // (wave-uniform)
+    return __fadd_rn(x, b);
+}
+
 // FP: APGPU_STACK_FRAME_PARAMS - prm.exp_ratio is float32 [3][N] = scale a, offset b, weight w of every frame; the column is
 // v = a x + b (two roundings) and the mean is the weighted mean of the survivors (see the end).  No calibration then.
-template <int NP, typename RawT, bool CALIB, bool FP = false>
+// LOC: APGPU_STACK_FRAME_LOCAL - a and b are read off per-frame meshes at the lane's pixel (local_map), the weights are
+// prm.lweight; everything behind the map is FP's.
+template <int NP, typename RawT, bool CALIB, bool FP = false, bool LOC = false>
 __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm)
 {
     static_assert(!(CALIB && FP), "fused calibration and frame parameters exclude each other");
+    static_assert(!(LOC && (CALIB || FP)), "the local map excludes the fused calibration and the per-frame parameters");
+    constexpr bool WT = FP || LOC;                           // the mean is the weighted mean of the survivors
     __shared__ float cols[NP * 64];
     const int lane = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * 64;
@@ -230,6 +279,19 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
     const int N = prm.N;
     const double inf = __builtin_inf();
     float v[NP];
+    MeshCell cell{};
+    int64_t cells = 0;
+    if constexpr (LOC) {                                     // (a lane behind the last pixel takes the block's first one)
+        const int64_t q = base + (valid ? lane : 0);
+        const int64_t row = q / prm.width;
+        const int y = (int)(prm.row0 + row), x = (int)(q - row * prm.width);
+        int j0, j1, k0, k1;
+        mesh_axis(y, prm.bh, prm.ny, j0, j1, cell.ty);
+        mesh_axis(x, prm.bw, prm.nx, k0, k1, cell.tx);
+        cell.i00 = j0 * prm.nx + k0; cell.i01 = j0 * prm.nx + k1;
+        cell.i10 = j1 * prm.nx + k0; cell.i11 = j1 * prm.nx + k1;
+        cells = (int64_t)prm.ny * prm.nx;
+    }
 
     // ---- the column: load, calibrate (stack_calibrate.h, load_column_exact: IEEE division, one value at a time) ----
     {
@@ -273,6 +335,7 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
                     if (dodiv) x = __fdiv_rn(x, nf);         // :463
                 }
                 if constexpr (FP) x = frame_map(x, prm.exp_ratio[f], prm.exp_ratio[N + f]);
+                if constexpr (LOC) x = local_map(x, prm.lscale, prm.loffset, cells, f, cell);
                 v[j + k] = j + k < N ? x : quiet_nan();
             }
         }
@@ -321,7 +384,7 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
             const int dlo = nlow > 0 ? nlow - lt : 0;
             const int keephi = nhigh > 0 ? eqhi - (nhigh - gt) : NP + 1;
             const bool uselo = nlow > 0, usehi = nhigh > 0;
-            if constexpr (FP) {
+            if constexpr (WT) {
                 mm_klo = uselo ? klo : 0u; mm_khi = usehi ? khi : 0xffffffffu;
                 mm_dlo = dlo; mm_keephi = keephi; mm_some = some;
             }
@@ -401,7 +464,7 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
             } else {
                 // the clip of this round (lanes without a round keep everything)
                 const double lo = active ? med - kl * sig : -inf, hi = active ? med + kh * sig : inf;
-                if constexpr (FP) {                          // (a lane without a round has -inf / +inf: no change)
+                if constexpr (WT) {                          // (a lane without a round has -inf / +inf: no change)
                     Lo = !(lo <= Lo) ? lo : Lo;              // (a NaN bound - sigma = inf on a constant column - keeps
                     Hi = !(hi >= Hi) ? hi : Hi;              //  nothing, here as in the round)
                 }
@@ -440,7 +503,7 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
     // repeated on it - Winsorized: finite and inside [Lo, Hi], for a removed value lies outside its round's interval and a kept one
     // inside every round's; min/max: the two key bounds and the tie counters over the finite values in frame order, as the
     // compaction above counted them - and num += double(w) double(v), den += double(w) run in frame order from +0.
-    if constexpr (FP) {
+    if constexpr (WT) {
         const int off = valid ? lane : 0;
         const RawT *const fb = static_cast<const RawT *>(prm.frames) + base + off;
         const bool mm = prm.minmax != 0;
@@ -458,8 +521,14 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
 #pragma unroll
             for (int k = 0; k < B; k++) {
                 const int f = j + k < N ? j + k : N - 1;
-                const float x = frame_map(to_f32(raw[k]), prm.exp_ratio[f], prm.exp_ratio[N + f]);
-                const float w = prm.exp_ratio[2 * N + f];
+                float x, w;
+                if constexpr (LOC) {
+                    x = local_map(to_f32(raw[k]), prm.lscale, prm.loffset, cells, f, cell);
+                    w = prm.lweight ? prm.lweight[f] : 1.f;
+                } else {
+                    x = frame_map(to_f32(raw[k]), prm.exp_ratio[f], prm.exp_ratio[N + f]);
+                    w = prm.exp_ratio[2 * N + f];
+                }
                 const bool fin = j + k < N && is_finite(x);
                 bool ok;
                 if (mm) {                                    // (wave-uniform)
@@ -492,24 +561,25 @@ __global__ __launch_bounds__(64) void stack_reject_kernel(const RejectParams prm
     }
 }
 
-template <int NP, typename RawT, bool CALIB, bool FP>
+template <int NP, typename RawT, bool CALIB, bool FP, bool LOC>
 int launch_one(const RejectParams &prm, hipStream_t st, char *describe)
 {
     if (describe) {
-        if (FP) snprintf(describe, 256, "stack_reject_kernel<%d, %s, false, true>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float");
+        if (LOC) snprintf(describe, 256, "stack_reject_kernel<%d, %s, false, false, true>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float");
+        else if (FP) snprintf(describe, 256, "stack_reject_kernel<%d, %s, false, true>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float");
         else snprintf(describe, 256, "stack_reject_kernel<%d, %s, %s>", NP, sizeof(RawT) == 2 ? "unsigned short" : "float", CALIB ? "true" : "false");
         return APGPU_OK;
     }
     const int64_t grid = (prm.P + 63) / 64;
     if (grid > 0x7fffffff) return fail(APGPU_EUNSUPPORTED, "stack (reject): n_pixels = %lld is too many for one launch", (long long)prm.P);
-    hipLaunchKernelGGL((stack_reject_kernel<NP, RawT, CALIB, FP>), dim3((unsigned)grid), dim3(64), 0, st, prm);
+    hipLaunchKernelGGL((stack_reject_kernel<NP, RawT, CALIB, FP, LOC>), dim3((unsigned)grid), dim3(64), 0, st, prm);
     return check_launch("stack kernel (reject)");
 }
 
-template <typename RawT, bool CALIB, bool FP = false>
+template <typename RawT, bool CALIB, bool FP = false, bool LOC = false>
 int launch_slots(const RejectParams &prm, hipStream_t st, char *describe)
 {
-#define APGPU_REJECT_TRY(NP) if (prm.N <= NP) return launch_one<NP, RawT, CALIB, FP>(prm, st, describe);
+#define APGPU_REJECT_TRY(NP) if (prm.N <= NP) return launch_one<NP, RawT, CALIB, FP, LOC>(prm, st, describe);
     APGPU_REJECT_SLOTS(APGPU_REJECT_TRY)
 #undef APGPU_REJECT_TRY
     return fail(APGPU_EUNSUPPORTED, "stack (reject): n_frames = %d exceeds APGPU_STACK_REJECT_MAX = %d", prm.N, APGPU_STACK_REJECT_MAX);
@@ -547,6 +617,20 @@ int launch_reject(const apgpu_stack_args *args, hipStream_t st, char *describe)
     } else {
         prm.kl = args->sigma_lower;
         prm.kh = args->sigma_upper;
+    }
+    if (args->flags & APGPU_STACK_FRAME_LOCAL) {             // (the descriptor on the host: stack_dispatch has checked it)
+        const apgpu_stack_local *loc = static_cast<const apgpu_stack_local *>(args->workspace);
+        prm.lscale = loc->scale;
+        prm.loffset = loc->offset;
+        prm.lweight = loc->weight;
+        prm.width = loc->width;
+        prm.row0 = loc->row0;
+        prm.bh = loc->box_height;
+        prm.bw = loc->box_width;
+        prm.ny = loc->ny;
+        prm.nx = loc->nx;
+        return args->dtype == APGPU_F32 ? launch_slots<float, false, false, true>(prm, st, describe)
+                                        : launch_slots<uint16_t, false, false, true>(prm, st, describe);
     }
     if (args->flags & APGPU_STACK_FRAME_PARAMS)              // (no calibration planes: stack_dispatch has seen to it)
         return args->dtype == APGPU_F32 ? launch_slots<float, false, true>(prm, st, describe) : launch_slots<uint16_t, false, true>(prm, st, describe);

@@ -373,7 +373,7 @@ def stack_sigclip(frames, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiter
 
 
 def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=None, nlow=1, nhigh=1,
-                 calib=None, pixmask=None, outputs=('mean',), scale=None, offset=None, weights=None):
+                 calib=None, pixmask=None, outputs=('mean',), scale=None, offset=None, weights=None, box=None, row0=0):
     """The rejection rules of small stacks (5 .. 30 registered light frames, where an outlier inflates the standard deviation
     a sigma clip judges it by), per pixel along N, at most _lib.STACK_REJECT_MAX (128) frames; include/apgpu.h has the definition.
 
@@ -385,8 +385,17 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
     -> dict of device tensors; the statistics are numpy's of the survivors in frame order, the float32 planes their roundings.
     scale / offset / weights (APGPU_STACK_FRAME_PARAMS; all None: not used): one value per frame, missing ones 1 / 0 / 1.  The
     rule then runs on v = float32(float32(scale_i x) + offset_i), and the mean is sum w_i v_i / sum w_i over the survivors
-    (float64, frame order); std and count stay unweighted.  Not together with calib; see frame_normalization."""
-    fp = _frame_params(frames, scale, offset, weights, calib)
+    (float64, frame order); std and count stay unweighted.  Not together with calib; see frame_normalization.
+    box (an int or (bh, bw); APGPU_STACK_FRAME_LOCAL): the LOCAL normalisation - frames is [N, H, W], offset a mesh [N, ny, nx]
+    with one value per bh x bw box (the geometry of box_clipped_stats), scale such a mesh or None (= 1), weights one value per
+    frame or None; a pixel's scale and offset are the meshes interpolated bilinearly between the box centres, held beyond the
+    outer ones (see local_stats / local_normalization).  row0: the image row of frames[:, 0] when frames is a row stripe
+    full[:, r0:r1] of the image the meshes describe."""
+    loc = fp = None
+    if box is not None:
+        loc = _frame_local(frames, scale, offset, weights, box, row0, calib)
+    else:
+        fp = _frame_params(frames, scale, offset, weights, calib)
     if method not in ('winsorized', 'minmax'):
         raise ValueError("method must be 'winsorized' or 'minmax', not %r" % (method,))
     bad = [k for k in outputs if k not in ('mean', 'std', 'count', 'mean_f64', 'std_f64')]
@@ -426,8 +435,72 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
         keep.append(block)
         a.exp_ratio = block.data_ptr()
         a.flags |= _lib.STACK_FRAME_PARAMS
+    if loc is not None:
+        # the meshes go up once, as one block each; the descriptor lives on the host until the call has returned
+        d = _lib.StackLocal()
+        d.width, d.row0 = frames.shape[2], int(row0)
+        d.box_height, d.box_width = loc['box']
+        d.ny, d.nx = loc['offset'].shape[1:]
+        for nm in ('scale', 'offset', 'weight'):
+            if loc[nm] is not None:
+                t = torch.from_numpy(loc[nm]).to(dev)
+                keep.append(t)
+                setattr(d, nm, t.data_ptr())
+        keep.append(d)
+        a.workspace, a.workspace_bytes = C.addressof(d), C.sizeof(d)
+        a.flags |= _lib.STACK_FRAME_LOCAL
     check(lib.apgpu_stack_sigclip(C.byref(a), _stream()))
     return res
+
+
+def _box_pair(box):
+    """box as (bh, bw): an int or a pair, each 1 .. 32768."""
+    bh, bw = (box, box) if np.ndim(box) == 0 else tuple(box)
+    if isinstance(bh, bool) or isinstance(bw, bool) or int(bh) != bh or int(bw) != bw or not (1 <= int(bh) <= 32768 and 1 <= int(bw) <= 32768):
+        raise ValueError('box must be a whole number or a pair (bh, bw) in 1 .. 32768, got %r' % (box,))
+    return int(bh), int(bw)
+
+
+def _frame_local(frames, scale, offset, weights, box, row0, calib):
+    """The meshes and weights of APGPU_STACK_FRAME_LOCAL on the host as float32, checked (the library cannot look at device
+    values): dict(box=(bh, bw), scale [N, ny, nx] or None, offset [N, ny, nx], weight [N] or None)."""
+    if calib is not None:
+        raise ValueError('box (the local normalisation) does not go with calib: it is for calibrated light frames')
+    if frames.dim() != 3:
+        raise ValueError('with box, frames must be [N, H, W]')
+    if isinstance(row0, bool) or int(row0) != row0 or int(row0) < 0:
+        raise ValueError('row0 must be a whole number >= 0, got %r' % (row0,))
+    N = frames.shape[0]
+    out = dict(box=_box_pair(box), scale=None, weight=None)
+    if offset is None:
+        raise ValueError('with box, offset is a mesh [N, ny, nx]')
+    shape = None
+    for nm, x in (('offset', offset), ('scale', scale)):
+        if x is None:
+            continue
+        if torch.is_tensor(x):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 3 or x.shape[0] != N or x.size == 0 or (shape is not None and x.shape != shape):
+            raise ValueError('%s must be a mesh [N, ny, nx] with N = %d%s, got shape %s'
+                             % (nm, N, '' if shape is None else ' of the shape of offset', x.shape))
+        shape = x.shape
+        with np.errstate(over='ignore'):
+            out[nm] = np.ascontiguousarray(x.astype(np.float32))
+        if not np.isfinite(out[nm]).all():
+            raise ValueError('%s must be finite (as float32)' % nm)
+    if weights is not None:
+        w = weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights
+        w = np.asarray(w, dtype=np.float64).reshape(-1)
+        if w.size != N:
+            raise ValueError('weights must hold one value per frame (%d), got %d' % (N, w.size))
+        with np.errstate(over='ignore'):
+            out['weight'] = w.astype(np.float32)
+        if not np.isfinite(out['weight']).all():
+            raise ValueError('weights must be finite (as float32)')
+        if not (out['weight'] > 0).all():
+            raise ValueError('weights must be > 0 (as float32)')
+    return out
 
 
 def _frame_params(frames, scale, offset, weights, calib):
@@ -523,6 +596,114 @@ def frame_normalization(stats, mode, reference=0, weighting=None):
     else:
         w = np.ones(N)
     return a, b, w
+
+
+def local_stats(frames, box, sigma=3.0, maxiters=5):
+    """Per frame and per box of bh x bw pixels (box: an int or (bh, bw)), the sigma-clipped median and standard deviation of the
+    box's finite pixels: box_clipped_stats(frames[i], None, bh, bw) for every frame, all N launches queued without a host
+    synchronisation in between.  frames: [N, H, W] float32 or uint16 (widened frame by frame).  Returns a float64
+    [N, ny, nx, 4] device tensor = median, std, survivors, pixels masked before clipping (outside the image or not finite);
+    what local_normalization takes."""
+    _need_cuda(frames)
+    if frames.dim() != 3:
+        raise ValueError('frames must be [N, H, W]')
+    bh, bw = _box_pair(box)
+    N, H, W = frames.shape
+    out = torch.empty((N, -(-H // bh), -(-W // bw), 4), dtype=torch.float64, device=frames.device)
+    for i in range(N):
+        f = frames[i] if frames.dtype == torch.float32 else widen_u16(frames[i], torch.float32)
+        out[i] = box_clipped_stats(f, None, bh, bw, sigma=sigma, maxiters=maxiters)
+    return out
+
+
+def local_normalization(stats, mode, reference=0, weighting=None, min_fraction=0.5, filter_size=1, box=None):
+    """Per-frame MESHES of scale a and offset b (and one weight per frame) that bring every box of every frame to the level the
+    reference frame has in that box: v = a(y, x) x + b(y, x) inside stack_reject(..., box=).  stats: [N, ny, nx, 4] from
+    local_stats (a device tensor costs one copy to the host; the rest is float64 NumPy on a few hundred numbers).
+
+    A box of frame i is USABLE when its survivors are at least min_fraction of the full box area bh * bw (box: as given to
+    local_stats; None: the largest survivors + masked count in stats stands in for the area) - so partial boxes at the edges
+    and resampling holes drop out - in frame i AND in the reference; for 'additive+scaling' and weighting='noise' both scales S
+    must also be > 0, for 'multiplicative' both locations L.  In usable boxes frame_normalization's table holds per box:
+
+        'additive'            a = 1 (scale is returned as None)   b = L_r - L_i
+        'multiplicative'      a = L_r / L_i                       b = 0
+        'additive+scaling'    a = S_r / S_i                       b = L_r - a L_i
+        'none'                a = 1 (None)                        b = 0
+
+    Unusable boxes are filled by inverse-distance weighting over the nearest usable ones (mesh.fill_excluded, as the sky-
+    background model does) and every mesh then passes a nanmedian filter of filter_size (mesh.nanmedian_filter; 1: none).  The
+    default is NO filter: the filter's windows are cut off at the mesh's rim, so the rim cells of a sloping mesh - the very thing
+    this normalisation is for - are pulled inwards by up to half a box of slope (DESIGN 4.1f has the figures); ask for 3 where
+    single boxes may be off and the sky is flat.  The reference frame is exactly (1, 0) everywhere.  A frame without one usable
+    box raises ValueError.
+    weighting 'noise': w_i = 1 / (median over frame i's usable boxes of a_i S_i)^2, divided by the largest; None: ones.
+    Returns (scale float32 [N, ny, nx] or None, offset float32 [N, ny, nx], weights float64 [N])."""
+    from .mesh import fill_excluded, nanmedian_filter
+    if mode not in NORMALIZE_MODES:
+        raise ValueError('normalize must be one of ' + ', '.join(NORMALIZE_MODES) + ', not %r' % (mode,))
+    if weighting == 'none':
+        weighting = None
+    if weighting not in (None, 'noise'):
+        raise ValueError("weighting must be None or 'noise', not %r" % (weighting,))
+    st = stats.detach().cpu().numpy() if torch.is_tensor(stats) else np.asarray(stats)
+    st = np.asarray(st, dtype=np.float64)
+    if st.ndim != 4 or st.shape[3] != 4 or st.size == 0:
+        raise ValueError('stats must be [N, ny, nx, 4] (median, std, survivors, masked)')
+    N = st.shape[0]
+    r = int(reference)
+    if not 0 <= r < N:
+        raise ValueError('reference = %d is not a frame index (N = %d)' % (r, N))
+    if not 0.0 <= float(min_fraction) <= 1.0:
+        raise ValueError('min_fraction must be in 0 .. 1, got %r' % (min_fraction,))
+    L, S, cnt = st[..., 0], st[..., 1], st[..., 2]
+    if box is None:
+        area = float((st[..., 2] + st[..., 3]).max())
+    else:
+        bh, bw = _box_pair(box)
+        area = float(bh * bw)
+    need_S = mode == 'additive+scaling' or weighting == 'noise'
+    ok = (cnt >= float(min_fraction) * area) & (cnt > 0) & np.isfinite(L) & np.isfinite(S)
+    if need_S:
+        ok &= S > 0
+    if mode == 'multiplicative':
+        ok &= L > 0
+    scaled = mode in ('multiplicative', 'additive+scaling')
+    A = np.ones(st.shape[:3])
+    B = np.zeros(st.shape[:3])
+    w = np.ones(N)
+    for i in range(N):
+        good = ok[i] & ok[r]
+        if not good.any():
+            raise ValueError('frame %d has no usable box (%s): nothing to normalise it by'
+                             % (i, 'none of its own' if not ok[i].any() else 'none shared with the reference frame %d' % r))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            if mode == 'additive':
+                a, b = np.ones_like(L[i]), L[r] - L[i]
+            elif mode == 'multiplicative':
+                a, b = L[r] / L[i], np.zeros_like(L[i])
+            elif mode == 'additive+scaling':
+                a = S[r] / S[i]
+                b = L[r] - a * L[i]
+            else:
+                a, b = np.ones_like(L[i]), np.zeros_like(L[i])
+        if weighting == 'noise':
+            w[i] = 1.0 / float(np.median((a * S[i])[good])) ** 2
+        if i == r:
+            continue                                         # exactly (1, 0) everywhere
+        if scaled:
+            A[i] = nanmedian_filter(fill_excluded(np.where(good, a, np.nan), good), int(filter_size))
+        if mode != 'none':
+            B[i] = nanmedian_filter(fill_excluded(np.where(good, b, np.nan), good), int(filter_size))
+    if weighting == 'noise':
+        if not np.isfinite(w).all():
+            raise ValueError('a frame has no measurable noise in its usable boxes: it cannot be weighted by it')
+        w = w / w.max()
+    with np.errstate(over='ignore'):
+        A32, B32 = A.astype(np.float32), B.astype(np.float32)
+    if not (np.isfinite(A32).all() and np.isfinite(B32).all()):
+        raise ValueError('the normalisation meshes are not finite as float32')
+    return (A32 if scaled else None), B32, w
 
 
 def stack_sigclip_chunked(frames, chunk=None, want_std=False, packed=False, finalize=True, exact=False, **clip):
@@ -1262,7 +1443,7 @@ COADD_COMBINE = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED'
 
 def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024,
           conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False, nlow=1, nhigh=1,
-          normalize='none', reference=0, weighting=None):
+          normalize='none', reference=0, weighting=None, norm_box=None):
     """Resample + combine: SWarp's COMBINE_TYPE MEDIAN / AVERAGE / WEIGHTED / SUM (resample_all.sh:60-73 add modes) plus
     CLIPPED (sigma-clipped mean, median-centred), WINSORIZED (Winsorized sigma clip at `sigma`, `maxiters` rounds) and MINMAX
     (the nlow lowest and nhigh highest values of a pixel dropped) - the two rules for stacks of few frames (stack_reject; up to
@@ -1277,7 +1458,11 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     those are the values that get compared.  WINSORIZED / MINMAX apply v = a x + b inside the kernel (stack_reject) and take
     weighting='noise' (the survivors' mean weighted by 1 / (a S)^2); the other modes get the same float32 map on the slab
     in place and take no weighting (WEIGHTED has `weights`).  The result then also holds scale, offset and norm_weights
-    (float64 numpy [N])."""
+    (float64 numpy [N]).
+    norm_box (an int or (bh, bw); WINSORIZED / MINMAX only): the LOCAL normalisation - the statistics are taken per box of the
+    resampled slab (local_stats), scale and offset are meshes interpolated at every pixel inside the kernel
+    (local_normalization, stack_reject(box=)): for frames whose sky differs in shape, not only in level.  The result then holds
+    the meshes as scale (None without a scaling mode) and offset (float32 numpy [N, ny, nx]), norm_weights and norm_box."""
     combine = combine.upper()
     if combine not in COADD_COMBINE:
         raise ValueError('combine must be one of ' + ', '.join(COADD_COMBINE))
@@ -1292,6 +1477,12 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     if weighting is not None and combine not in ('WINSORIZED', 'MINMAX'):
         raise ValueError('weighting goes with combine WINSORIZED and MINMAX only (WEIGHTED takes weights), not with %s' % combine)
     normed = normalize != 'none' or weighting is not None
+    if norm_box is not None:
+        norm_box = _box_pair(norm_box)
+        if combine not in ('WINSORIZED', 'MINMAX'):
+            raise ValueError('norm_box (the local normalisation) goes with combine WINSORIZED and MINMAX only, not with %s '
+                             '(MINMAX with nlow = nhigh = 0 is the normalised, weighted average)' % combine)
+        normed = True
     if fused and normed:
         raise ValueError('fused=True does not go with a normalisation: the statistics are taken on the resampled slab')
     if combine in ('WINSORIZED', 'MINMAX') and frames.dim() == 3 and frames.shape[0] > _lib.STACK_REJECT_MAX:
@@ -1307,6 +1498,14 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     else:
         res, _ = resample_affine(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, n_phases=n_phases, weight=False,
                                  conserve_flux=conserve_flux)
+    if norm_box is not None:
+        if res.dim() != 3:
+            raise ValueError('norm_box needs frames [N, H, W]')
+        a, b, w = local_normalization(local_stats(res, norm_box, sigma=3.0, maxiters=5), normalize, reference=reference,
+                                      weighting=weighting, box=norm_box)
+        kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'WINSORIZED' else dict(nlow=nlow, nhigh=nhigh)
+        r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, box=norm_box, **kw)
+        return dict(image=r['mean'], count=r['count'], scale=a, offset=b, norm_weights=w, norm_box=norm_box)
     if normed:
         a, b, w = frame_normalization(frame_stats(res, sigma=3.0, maxiters=5), normalize, reference=reference, weighting=weighting)
         extra = dict(scale=a, offset=b, norm_weights=w)

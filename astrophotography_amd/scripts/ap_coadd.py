@@ -41,6 +41,10 @@ def command_line_opts(argv):
     parser.add_argument('--weighting', default='none', choices=['none', 'noise'],
                         help='WINSORIZED and MINMAX: average the surviving values with inverse-variance weights of the '
                              'normalised frames. Default: none')
+    parser.add_argument('--norm_box', default=None, type=int, metavar='PIXELS',
+                        help='WINSORIZED and MINMAX: normalise LOCALLY - the statistics are taken per box of PIXELS x PIXELS and scale and '
+                             'offset are interpolated at every pixel, for frames whose sky differs in shape (moon, light dome, '
+                             'meridian flip). Default: one scale and one offset per frame')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
     return parser.parse_args(argv)
 
@@ -69,7 +73,7 @@ def main(args=None):
         out_shape = (ny, nx)
     rs = ApResample(p.loglevel, combine=p.combine, sigma=p.sigma, maxiters=None if p.maxiters < 0 else p.maxiters,
                     oversampling=p.oversampling, gain_keyword=p.gain_keyword, nlow=p.nlow, nhigh=p.nhigh, normalize=p.normalize, reference=p.reference,
-                    weighting=None if p.weighting == 'none' else p.weighting)
+                    weighting=None if p.weighting == 'none' else p.weighting, norm_box=p.norm_box)
     center = None
     if p.center:
         center = tuple(float(v) for v in p.center.split(','))

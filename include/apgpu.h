@@ -190,7 +190,8 @@ typedef struct apgpu_stack_args {
 
 /* The rejection rules of SMALL stacks (5 .. 30 registered light frames, where an outlier inflates the very standard deviation
  * a sigma clip judges it by): Winsorized sigma clipping and min/max rejection, through apgpu_stack_sigclip.  The two bits are
- * mutually exclusive.  With either: one launch, float64 arithmetic, `workspace` is never read or written;
+ * mutually exclusive.  With either: one launch, float64 arithmetic, `workspace` is never read or written (APGPU_STACK_FRAME_LOCAL
+ * below reads a descriptor there, on the host);
  * APGPU_STACK_EXACT_MOMENTS, APGPU_STACK_MOMENTS_MEAN and APGPU_STACK_SINGLE_KERNEL are accepted and have no effect;
  * center must be APGPU_CENTER_MEDIAN and dev APGPU_DEV_STD, APGPU_STACK_NONFINITE_UNCLIPPED is APGPU_EINVAL; outputs are
  * mean, std, count, mean_f64, std_f64 (`moments` or `median` != NULL: APGPU_EUNSUPPORTED); n_frames <= APGPU_STACK_REJECT_MAX
@@ -239,6 +240,40 @@ typedef struct apgpu_stack_args {
  *       den += double(w_k)
  *   which is np.cumsum(...)[-1] of the terms; mean = mean_f64 rounded once.  No survivor or a masked pixel: NaN and count 0. */
 #define APGPU_STACK_FRAME_PARAMS 64
+
+/* APGPU_STACK_FRAME_LOCAL: LOCAL normalisation inside the two rejection rules - one scale and one offset per frame level the
+ * sky, but not its shape: a rising moon, a light dome or a meridian flip leave a gradient of tens of ADU between the frames of a
+ * pixel, which the rule takes for the column's sigma.  With the bit, scale and offset of a frame are MESHES (one value per
+ * box_height x box_width box, the geometry of apgpu_box_clipped_stats_f32) interpolated bilinearly at every pixel.  Valid only
+ * together with exactly one of APGPU_STACK_REJECT_WINSORIZED / APGPU_STACK_REJECT_MINMAX (without: APGPU_EUNSUPPORTED;
+ * apgpu_stack_median and apgpu_resample_stack_sigclip: APGPU_EUNSUPPORTED); not together with APGPU_STACK_FRAME_PARAMS
+ * (APGPU_EINVAL); bias, dark, nflat, pedestal and exp_ratio must be NULL (APGPU_EINVAL).
+ *   `workspace` - which the rejection rules otherwise never look at - is a HOST pointer to an apgpu_stack_local, and
+ *   workspace_bytes must be sizeof(apgpu_stack_local).  The library reads it on the host during the call and checks what it
+ *   can see (APGPU_EINVAL: width < 1 or not a divisor of n_pixels, row0 < 0, a box side outside 1 .. 32768, ny or nx < 1,
+ *   ny * nx >= 2^31, offset NULL, image rows or columns beyond 2^30).  The CALLER guarantees finite meshes and finite weights
+ *   > 0.  The mesh need not cover the image: beyond the outer box centres the outer values hold.
+ *   pixmask, frame_stride (row stripes: row0), both dtypes, the outputs and APGPU_STACK_REJECT_MAX are as without the bit.
+ * Definition (no contraction; every operation rounds once in float32).  Box centres lie at (j + 0.5) box - 0.5.  Per axis, with
+ * c the pixel coordinate, b the box size and m the mesh extent (whole-number arithmetic, exact; one IEEE division):
+ *     u = 2c + 1 - b;  j0 = clamp(floor(u / 2b), 0, max(m - 2, 0));  j1 = min(j0 + 1, m - 1)
+ *     t = float32(clamp(u - 2 b j0, 0, 2b)) / float32(2b)
+ * (j0, j1, ty) from the image row y = row0 + p / width, (k0, k1, tx) from the column x = p % width.  For a mesh M of frame i:
+ *     top = M[j0][k0] + tx * (M[j0][k1] - M[j0][k0]);  bot = the same on row j1;  m(y, x) = top + ty * (bot - top)
+ *   x_raw = the raw value as float32;  v = float32(float32(a(y, x) * x_raw) + b(y, x));  scale == NULL: v = float32(x_raw + b),
+ *   the bits a mesh of ones gives.  From here on the definition of APGPU_STACK_FRAME_PARAMS holds word for word: S = the finite
+ *   v in frame order, the rule unchanged, count and std_f64 unweighted, mean_f64 = num / den over the survivors with weight[i]
+ *   (NULL: 1).  A mesh that is constant per frame gives the bits of APGPU_STACK_FRAME_PARAMS with those scalars. */
+#define APGPU_STACK_FRAME_LOCAL 128
+typedef struct apgpu_stack_local {
+    int64_t width;                  /* pixel p of the call is image row row0 + p / width, column p % width; n_pixels % width == 0 */
+    int64_t row0;                   /* image row of the call's first pixel (row stripes); >= 0 */
+    int32_t box_height, box_width;  /* 1 .. 32768 */
+    int32_t ny, nx;                 /* mesh shape, >= 1 */
+    const float *scale;             /* device float32 [n_frames][ny][nx], or NULL = 1 everywhere */
+    const float *offset;            /* device float32 [n_frames][ny][nx], not NULL */
+    const float *weight;            /* device float32 [n_frames], or NULL = 1 */
+} apgpu_stack_local;
 
 /* The two-kernel scheme and its workspace.  A clipped stack of up to 128 frames (and the chunked kernel for 129 .. 512) with
  * lean outputs runs as a FAST kernel - the float32 fast path alone, four wavefronts per SIMD - followed by a REDO PASS of the
