@@ -557,6 +557,13 @@ __global__ __launch_bounds__(256, NP <= 64 ? APGPU_FAST_MIN_BLOCKS : ((FULL || P
     // column), so theirs are longer (a core of four values is enough for the sums' four chains)
     constexpr int T = !CALIB ? (NP >= 20 ? 8 : 6) : fast_kernel_tail(NP, FULL);
     constexpr bool HALVES = CALIB && NP >= 104;             // the raw column in two halves: v[] + half of raw[] fit two wavefronts per SIMD
+    // round 8: the benchmark's kernel (64 full slots of float32 frames, fused calibration, tails of 4; both tile copies and the
+    // PLUS form) SELECTS the 14 ranks the clip reads instead of sorting (stack_sort.h, kSelect64); nothing here completes the sort
+#ifdef APGPU_VARIANT_NO_SELECT
+    constexpr bool SELECT = false;                          // (measurement only, tools/variant_lib.sh: the pruned sorting network)
+#else
+    constexpr bool SELECT = NP == 64 && sizeof(RawT) == 4 && CALIB && FULL && PADS == 0 && T == 4;
+#endif
     const int64_t base = (int64_t)blockIdx.x * 256;
     const int lane = threadIdx.x;
     const int64_t p = base + lane;
@@ -632,7 +639,7 @@ __global__ __launch_bounds__(256, NP <= 64 ? APGPU_FAST_MIN_BLOCKS : ((FULL || P
             // kernel that ships, same control flow up to the cut, same residency: the LDS block below holds it at four workgroups per CU)
             if (wave_any(good)) {
                 if (APGPU_VARIANT_STRIP == 1) {
-                    sort_column<NP, T, CALIB>(v);
+                    sort_column<NP, T, CALIB, SELECT>(v);
                     if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN, true>(v, dodiv, N, plo);
                 }
                 float acc[4] = {good ? 0.f : 1.f, 0.f, 0.f, 0.f};
@@ -645,7 +652,7 @@ __global__ __launch_bounds__(256, NP <= 64 ? APGPU_FAST_MIN_BLOCKS : ((FULL || P
             if (wave_any(good)) {
                 // (calibrated columns: no finite test so far - calibrate_fast's FINITE_LATER; the sort carries a NaN to the last
                 // slot and range_ok_sorted reads it, and an infinity, off the ends)
-                sort_column<NP, T, CALIB>(v);
+                sort_column<NP, T, CALIB, SELECT>(v);
                 if constexpr (CALIB) good = good && range_ok_sorted<NP, MINN, true>(v, dodiv, N, plo);
                 else {
                     // the sentinels sit at the top: count them in the upper tail (pads included); a full tail = too many

@@ -373,11 +373,98 @@ __device__ __forceinline__ void opnet_from(float (&v)[NP])
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Round 8: a SELECTION network for 64 slots with tails of 4.  clip_fast32 reads 16 of the 64 ranks in order - the tails 0..3 and
+// 60..63, the first value behind either tail (4 and 59: trim_low_fast / trim_high_fast ask it whether a fifth value would go),
+// the median window 29..34 - and only sums the other 48; make_opnet<64, 4> is a SORTING network pruned by backward liveness,
+// which keeps nearly all of it (750 instructions; its last layer happens to deliver ranks 4 and 59 with their neighbours).  This
+// one never builds sorted 16- or 32-blocks.  The column is an 8 x 8 matrix in wire order (wire = 8 row + column):
+//   1. the 8 rows are sorted with kSort8Ops, 2. the 8 columns likewise - the rows stay sorted - 16 x 24 = 384 instructions;
+//   3. a 0-1 input with sorted rows and columns is one of C(16, 8) = 12870 staircase matrices, so whatever follows is verified
+//      EXHAUSTIVELY in no time, which makes it searchable: kSelect8x8Ops is the post-phase found by tools/search_select_grid.py
+//      (Batcher's 64-network on those wires, what never swaps dropped, sorters removed greedily, then local search: sorters
+//      fused into 3-sorters, widened, moved, with greedy removal after every move; cost = instructions).
+// What it delivers, checked on every staircase case by the search and again, with the 8-sorter on its 2^8 inputs and random float
+// columns against std::sort, by tools/netsearch/verify_select64.cpp (= tests/test_select_network_host.py):
+//   - standard form: every sorter lists its wires ascending, so an ascending column passes through unchanged;
+//   - wires 0..4, 29..34, 59..63 carry exactly those ranks (wire 0 the minimum, wire 63 the maximum: range_ok_sorted reads the
+//     ends, and NANMAX's argument at cmpx holds as for any network whose last output is the maximum);
+//   - every value on wires 4..28 is <= every value on wires 35..59: clip_fast32 sums the core in mirror pairs (i, 63 - i), and
+//     each half staying on its side of the median window keeps that pairing's cancellation.  The core's ORDER within a half is
+//     not the sorted one, so S is rounded differently than behind make_opnet (same chains, same number of terms, same budget).
+// -------------------------------------------------------------------------------------------------
+// the post-phase: 205 instructions (8 compare-exchanges, 63 3-sorters); with the rows and columns 589
+constexpr NetOp kSelect8x8Ops[71] = {
+    {{39, 61, 0, 0}, 2}, {{22, 26, 28, 0}, 3}, {{1, 8, 0, 0}, 2}, {{21, 25, 0, 0}, 2}, {{33, 36, 40, 0}, 3}, {{38, 42, 0, 0}, 2},
+    {{7, 11, 0, 0}, 2}, {{50, 52, 56, 0}, 3}, {{6, 10, 12, 0}, 3}, {{2, 20, 24, 0}, 3}, {{23, 25, 27, 0}, 3}, {{34, 42, 50, 0}, 3},
+    {{35, 37, 41, 0}, 3}, {{39, 41, 43, 0}, 3}, {{11, 25, 44, 0}, 3}, {{5, 9, 10, 0}, 3}, {{4, 16, 37, 0}, 3}, {{11, 12, 13, 0}, 3},
+    {{22, 23, 24, 0}, 3}, {{34, 35, 48, 0}, 3}, {{38, 39, 40, 0}, 3}, {{55, 59, 62, 0}, 3}, {{10, 19, 22, 0}, 3}, {{11, 19, 40, 0}, 3},
+    {{15, 23, 55, 0}, 3}, {{40, 48, 58, 0}, 3}, {{44, 48, 52, 0}, 3}, {{14, 18, 22, 0}, 3}, {{15, 18, 19, 0}, 3}, {{12, 20, 24, 0}, 3},
+    {{30, 48, 0, 0}, 2}, {{15, 34, 36, 0}, 3}, {{13, 19, 21, 0}, 3}, {{19, 22, 26, 0}, 3}, {{47, 54, 60, 0}, 3}, {{41, 42, 49, 0}, 3},
+    {{23, 26, 29, 0}, 3}, {{2, 4, 8, 0}, 3}, {{39, 53, 57, 0}, 3}, {{3, 4, 5, 0}, 3}, {{21, 22, 24, 0}, 3}, {{23, 24, 25, 0}, 3},
+    {{38, 39, 41, 0}, 3}, {{18, 19, 20, 0}, 3}, {{25, 26, 28, 0}, 3}, {{20, 35, 36, 0}, 3}, {{37, 38, 40, 0}, 3}, {{39, 40, 42, 0}, 3},
+    {{41, 42, 44, 0}, 3}, {{27, 30, 51, 0}, 3}, {{59, 60, 61, 0}, 3}, {{22, 30, 38, 0}, 3}, {{19, 31, 39, 0}, 3}, {{39, 54, 59, 0}, 3},
+    {{26, 34, 42, 0}, 3}, {{27, 29, 53, 0}, 3}, {{27, 28, 44, 0}, 3}, {{27, 33, 35, 0}, 3}, {{24, 36, 40, 0}, 3}, {{25, 33, 41, 0}, 3},
+    {{18, 34, 40, 0}, 3}, {{23, 31, 35, 0}, 3}, {{28, 32, 36, 0}, 3}, {{21, 29, 37, 0}, 3}, {{9, 29, 33, 0}, 3}, {{30, 34, 0, 0}, 2},
+    {{23, 29, 0, 0}, 2}, {{29, 30, 32, 0}, 3}, {{31, 32, 33, 0}, 3}, {{33, 34, 36, 0}, 3}, {{4, 8, 28, 0}, 3}};
+
+constexpr OpNet<64> make_select64()
+{
+    OpNet<64> net{};
+    net.n = 0;
+    for (int r = 0; r < 8; r++)
+        for (const NetOp &o : kSort8Ops)
+            net.op[net.n++] = NetOp{{(unsigned char)(8 * r + o.w[0]), (unsigned char)(8 * r + o.w[1]), (unsigned char)(8 * r + o.w[2]), 0}, 3, 0};
+    for (int c = 0; c < 8; c++)
+        for (const NetOp &o : kSort8Ops)
+            net.op[net.n++] = NetOp{{(unsigned char)(8 * o.w[0] + c), (unsigned char)(8 * o.w[1] + c), (unsigned char)(8 * o.w[2] + c), 0}, 3, 1};
+    for (const NetOp &o : kSelect8x8Ops) {
+        net.op[net.n] = o;
+        net.op[net.n++].stage = 2;
+    }
+    return net;
+}
+
+inline constexpr OpNet<64> kSelect64 = make_select64();
+
+template <int I, bool NANMAX>
+__device__ __forceinline__ void select64_apply(float (&v)[64])
+{
+    constexpr NetOp o = kSelect64.op[I];
+    if constexpr (o.k == 2) cmpx<NANMAX>(v[o.w[0]], v[o.w[1]]);
+    else if constexpr (o.k == 3) sort3<NANMAX>(v[o.w[0]], v[o.w[1]], v[o.w[2]]);
+    else sort4<NANMAX>(v[o.w[0]], v[o.w[1]], v[o.w[2]], v[o.w[3]]);
+}
+
+template <int BASE, bool NANMAX, int... I>
+__device__ __forceinline__ void select64_chunk(float (&v)[64], std::integer_sequence<int, I...>)
+{
+    (select64_apply<BASE + I, NANMAX>(v), ...);
+}
+
+template <int BASE = 0, bool NANMAX = false>
+__device__ __forceinline__ void select64_from(float (&v)[64])
+{
+    constexpr int total = kSelect64.n;
+    constexpr int CH = 64;
+    if constexpr (BASE < total) {
+        constexpr int len = (total - BASE < CH) ? total - BASE : CH;
+        select64_chunk<BASE, NANMAX>(v, std::make_integer_sequence<int, len>{});
+        select64_from<BASE + len, NANMAX>(v);
+    }
+}
+
 // PRUNE_T > 0: only the outputs clip_fast32 reads come out sorted (make_pruned_net / make_opnet).
 // NANMAX: NaN-propagating maxima - a NaN in the column comes out on v[NP - 1] (see cmpx).
-template <int NP, int PRUNE_T = 0, bool NANMAX = false>
+// SELECT (off by default; 64 slots with tails of 4 only): the selection network above instead of the pruned sorting network -
+// the same needed wires; the core is not left in the same order.
+template <int NP, int PRUNE_T = 0, bool NANMAX = false, bool SELECT = false>
 __device__ __forceinline__ void sort_column(float (&v)[NP])
 {
+    if constexpr (SELECT) {
+        static_assert(NP == 64 && PRUNE_T == 4, "the selection network: 64 slots, tails of 4");
+        select64_from<0, NANMAX>(v);
+    } else
 #ifndef APGPU_VARIANT_BATCHER_ONLY
     if constexpr (NP >= 8 && NP % 4 == 0) {
         opnet_from<NP, PRUNE_T, 0, NANMAX>(v);
