@@ -18,6 +18,7 @@ STACK_EXACT_MOMENTS, STACK_MOMENTS_MEAN, STACK_SINGLE_KERNEL, STACK_NONFINITE_UN
 STACK_REJECT_WINSORIZED, STACK_REJECT_MINMAX = 16, 32   # apgpu_stack_args.flags: the rejection rules of small stacks (ops.stack_reject)
 STACK_FRAME_PARAMS = 64                                 # APGPU_STACK_FRAME_PARAMS: exp_ratio = float32 [3][N] scale, offset, weight (with a rejection rule)
 STACK_FRAME_LOCAL = 128                                 # APGPU_STACK_FRAME_LOCAL: workspace = a host StackLocal (scale / offset meshes; with a rejection rule)
+STACK_REJECT_ESD = 256                                  # APGPU_STACK_REJECT_ESD: the generalized ESD test; workspace = a host StackEsd
 STACK_REJECT_MAX = 128                                # APGPU_STACK_REJECT_MAX: frames a rejection rule takes
 CCDPROC_FORM = {'astropy': 0, 'legacy': 1}                                  # APGPU_CCDPROC_*
 STACK_WS_STATS_OFFSET = 16384                           # APGPU_STACK_WS_STATS_OFFSET: int64 calls, pixels, pixels listed, 64-pixel blocks given up
@@ -63,6 +64,12 @@ class StackLocal(C.Structure):
         ('width', C.c_int64), ('row0', C.c_int64), ('box_height', C.c_int32), ('box_width', C.c_int32),
         ('ny', C.c_int32), ('nx', C.c_int32), ('scale', C.c_void_p), ('offset', C.c_void_p), ('weight', C.c_void_p),
     ]
+
+
+class StackEsd(C.Structure):
+    """struct apgpu_stack_esd (include/apgpu.h): the descriptor APGPU_STACK_REJECT_ESD finds in StackArgs.workspace (lambda_ is its
+    member `lambda`: the critical values on the device; local: a host StackLocal's address with APGPU_STACK_FRAME_LOCAL)."""
+    _fields_ = [('lambda_', C.c_void_p), ('max_outliers', C.c_int32), ('reserved', C.c_int32), ('local', C.c_void_p)]
 
 
 # name -> (restype, argtypes); every symbol include/apgpu.h declares

@@ -17,13 +17,15 @@ import numpy as np
 from .. import __version__, fitsio
 from . import _common
 
-COMBINE_TYPES = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX')
+COMBINE_TYPES = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX', 'ESD')
+REJECT_TYPES = ('WINSORIZED', 'MINMAX', 'ESD')      # ops.stack_reject's rules: weighting and norm_box go with them
 NORMALIZE_MODES = ('none', 'additive', 'multiplicative', 'additive+scaling')
 
 
 class ApResample:
     def __init__(self, loglevel='INFO', combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024, conserve_flux=True, oversampling=1,
-                 gain_keyword='EGAIN', nlow=1, nhigh=1, normalize='none', reference=0, weighting=None, norm_box=None):
+                 gain_keyword='EGAIN', nlow=1, nhigh=1, normalize='none', reference=0, weighting=None, norm_box=None,
+                 esd_outliers=0.3, esd_significance=0.05, esd_low_relaxation=1.5):
         self._name = 'ApResample'
         self._logger = _common.make_logger(self._name, loglevel)
         combine = str(combine).upper()
@@ -31,6 +33,8 @@ class ApResample:
             raise ValueError(f'Error, combine type {combine} is not one of the allowed types: {COMBINE_TYPES}')
         self.combine, self.sigma, self.maxiters, self.n_phases = combine, sigma, maxiters, n_phases
         self.nlow, self.nhigh = int(nlow), int(nhigh)       # MINMAX: values dropped per pixel at either end
+        # ESD: the largest fraction of outliers, the significance level, the low relaxation (ops.stack_reject)
+        self.esd_outliers, self.esd_significance, self.esd_low_relaxation = float(esd_outliers), float(esd_significance), float(esd_low_relaxation)
         self.conserve_flux = bool(conserve_flux)            # FSCALASTRO_TYPE VARIABLE (resample_all.sh:129)
         self.oversampling = int(oversampling)               # OVERSAMPLING (resample_all.sh:112: 4)
         self.gain_keyword = gain_keyword                    # GAIN_KEYWORD (resample_all.sh:111: EGAIN)
@@ -43,7 +47,7 @@ class ApResample:
         weighting = None if weighting in (None, 'none') else str(weighting).lower()
         if weighting not in (None, 'noise'):
             raise ValueError(f"Error, weighting {weighting} is not one of: none, noise")
-        if weighting is not None and combine not in ('WINSORIZED', 'MINMAX'):
+        if weighting is not None and combine not in REJECT_TYPES:
             raise ValueError(f'Error, weighting {weighting} goes with combine WINSORIZED and MINMAX only, not {combine}.')
         self.normalize, self.weighting = normalize, weighting
         self.reference = reference                          # a frame index, or (coadd_files) a file name
@@ -51,7 +55,7 @@ class ApResample:
         if norm_box is not None:
             if isinstance(norm_box, bool) or int(norm_box) != norm_box or not 1 <= int(norm_box) <= 32768:
                 raise ValueError(f'Error, norm_box {norm_box} is not a whole number of pixels in 1..32768')
-            if combine not in ('WINSORIZED', 'MINMAX'):
+            if combine not in REJECT_TYPES:
                 raise ValueError(f'Error, norm_box goes with combine WINSORIZED and MINMAX only, not {combine}.')
             norm_box = int(norm_box)
         self.norm_box = norm_box
@@ -61,8 +65,11 @@ class ApResample:
         form (CLIPPED / AVERAGE of up to 16 frames, no resampled slab in memory).  With a normalisation the result also holds
         scale, offset and norm_weights per frame (with norm_box: scale and offset meshes [N, ny, nx], and norm_box); reference: the frame index (default: the constructor's)."""
         from .. import ops
+        esd = {}
+        if self.combine == 'ESD':
+            esd = dict(esd_outliers=self.esd_outliers, esd_significance=self.esd_significance, esd_low_relaxation=self.esd_low_relaxation)
         if self.normalize != 'none' or self.weighting is not None or self.norm_box is not None:
-            kw = {} if self.norm_box is None else dict(norm_box=self.norm_box)
+            kw = dict(esd) if self.norm_box is None else dict(esd, norm_box=self.norm_box)
             ref = self.reference if reference is None else reference
             return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                              sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
@@ -71,7 +78,7 @@ class ApResample:
         return ops.coadd(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, combine=self.combine,
                          sigma=self.sigma, maxiters=self.maxiters, n_phases=self.n_phases, conserve_flux=self.conserve_flux,
                          oversampling=self.oversampling, weights=weights, fine_affines=fine_affines, fused=fused,
-                         nlow=self.nlow, nhigh=self.nhigh)
+                         nlow=self.nlow, nhigh=self.nhigh, **esd)
 
     def _output_gain(self, gains, fscale, weights):
         """Effective gain of the co-add in electrons per output unit, written as GAIN when every input carries the
@@ -190,6 +197,10 @@ class ApResample:
         elif self.combine == 'MINMAX':
             hdr['COMBNLO'] = (self.nlow, 'Lowest values dropped per pixel')
             hdr['COMBNHI'] = (self.nhigh, 'Highest values dropped per pixel')
+        elif self.combine == 'ESD':
+            hdr['COMBESO'] = (self.esd_outliers, 'ESD test, largest fraction of outliers')
+            hdr['COMBESS'] = (self.esd_significance, 'ESD test, significance level')
+            hdr['COMBESR'] = (self.esd_low_relaxation, 'ESD test, low relaxation')
         if 'scale' in res:
             hdr['NORMMODE'] = (self.normalize, 'Frame normalisation before the combine')
             hdr['NORMREF'] = (Path(input_files[ref]).name, 'Reference frame of the normalisation')

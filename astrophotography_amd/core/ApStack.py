@@ -15,8 +15,8 @@ import numpy as np
 from .. import __version__, fitsio
 from . import _common
 
-METHODS = ('sigclip', 'median', 'mean', 'winsorized', 'minmax')
-REJECT_METHODS = ('winsorized', 'minmax')         # ops.stack_reject: the rules for stacks of few frames
+METHODS = ('sigclip', 'median', 'mean', 'winsorized', 'minmax', 'esd')
+REJECT_METHODS = ('winsorized', 'minmax', 'esd')  # ops.stack_reject: the rules for stacks of few frames, and the ESD test
 
 
 def _apply_pedestals(slab, hdrs):
@@ -34,12 +34,16 @@ def _apply_pedestals(slab, hdrs):
 
 class ApStack:
     def __init__(self, loglevel='INFO', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=5, cenfunc='median',
-                 stdfunc='std', nlow=1, nhigh=1):
+                 stdfunc='std', nlow=1, nhigh=1, esd_outliers=0.3, esd_significance=0.05, esd_low_relaxation=1.5):
         self._name = 'ApStack'
         self._logger = _common.make_logger(self._name, loglevel)
         self.sigma, self.sigma_lower, self.sigma_upper = sigma, sigma_lower, sigma_upper
         self.maxiters, self.cenfunc, self.stdfunc = maxiters, cenfunc, stdfunc
         self.nlow, self.nhigh = nlow, nhigh
+        self.esd_outliers, self.esd_significance, self.esd_low_relaxation = esd_outliers, esd_significance, esd_low_relaxation
+
+    def _esd_kw(self):
+        return dict(esd_outliers=self.esd_outliers, esd_significance=self.esd_significance, esd_low_relaxation=self.esd_low_relaxation)
 
     def stack(self, frames, method='sigclip', calib=None, pixmask=None, outputs=('mean',), normalize='none', reference=0,
               weighting=None, norm_box=None):
@@ -49,7 +53,10 @@ class ApStack:
         'mean': plain mean (a clip with an infinite bound, one pass); 'median': np.nanmedian along N;
         'winsorized': Winsorized sigma clip at sigma / sigma_lower / sigma_upper, maxiters rounds, and 'minmax': the nlow
         lowest and nhigh highest values of a pixel dropped - the rules for 5 .. 30 frames, at most 128 (ops.stack_reject;
-        outputs 'mean', 'std', 'count', 'mean_f64', 'std_f64').  Those two take normalize ('additive', 'multiplicative',
+        outputs 'mean', 'std', 'count', 'mean_f64', 'std_f64'); 'esd': the generalized ESD test for a couple of dozen frames and
+        more, through the same call - at most the fraction esd_outliers of a pixel's values may go, the largest prefix of
+        removals significant at esd_significance does, a low value's deviation counts divided by esd_low_relaxation.  Those
+        three take normalize ('additive', 'multiplicative',
         'additive+scaling': the frames brought to frame `reference`'s level inside the kernel, ops.frame_stats /
         ops.frame_normalization) and weighting='noise' (the survivors averaged with inverse-variance weights) on a slab that is
         not calibrated in the same call; the result then also holds scale, offset and norm_weights (float64 numpy [N]).
@@ -77,7 +84,7 @@ class ApStack:
                                               weighting=None if weighting in (None, 'none') else weighting, box=norm_box)
             res = ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
                                    maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, pixmask=pixmask, outputs=outputs,
-                                   scale=a, offset=b, weights=w, box=norm_box)
+                                   scale=a, offset=b, weights=w, box=norm_box, **self._esd_kw())
             res.update(scale=a, offset=b, norm_weights=w, norm_box=ops._box_pair(norm_box))
             return res
         if method in REJECT_METHODS:
@@ -90,12 +97,12 @@ class ApStack:
                                                   weighting=None if weighting in (None, 'none') else weighting)
                 res = ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
                                        maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, pixmask=pixmask, outputs=outputs,
-                                       scale=a, offset=b, weights=w)
+                                       scale=a, offset=b, weights=w, **self._esd_kw())
                 res.update(scale=a, offset=b, norm_weights=w)
                 return res
             return ops.stack_reject(frames, method, sigma=self.sigma, sigma_lower=self.sigma_lower, sigma_upper=self.sigma_upper,
                                     maxiters=self.maxiters, nlow=self.nlow, nhigh=self.nhigh, calib=calib, pixmask=pixmask,
-                                    outputs=outputs)
+                                    outputs=outputs, **self._esd_kw())
         if frames.shape[0] > MAX_STACK and method != 'median':
             # beyond what one launch reduces exactly (512 frames): chunks, float64 moments added (ops.stack_sigclip_chunked)
             want = set(outputs) - {'mean', 'count', 'std'}
@@ -170,6 +177,10 @@ class ApStack:
         elif method == 'minmax':
             hdr['STACKNLO'] = (int(self.nlow), 'Lowest values dropped per pixel')
             hdr['STACKNHI'] = (int(self.nhigh), 'Highest values dropped per pixel')
+        elif method == 'esd':
+            hdr['STACKESO'] = (float(self.esd_outliers), 'ESD test, largest fraction of outliers')
+            hdr['STACKESS'] = (float(self.esd_significance), 'ESD test, significance level')
+            hdr['STACKESR'] = (float(self.esd_low_relaxation), 'ESD test, low relaxation')
         for idx, fname in enumerate(input_files):
             hdr[f'IFILE{idx:03d}'] = Path(fname).name
         for k, v in (extra_keywords or {}).items():
@@ -182,6 +193,9 @@ class ApStack:
                               f'maxiters={hdr["STACKITR"]}')
         elif method == 'minmax':
             hdr['HISTORY'] = f'Min/max rejection: nlow={int(self.nlow)} nhigh={int(self.nhigh)}'
+        elif method == 'esd':
+            hdr['HISTORY'] = (f'Generalized ESD test: outliers={hdr["STACKESO"]} significance={hdr["STACKESS"]} '
+                              f'low_relaxation={hdr["STACKESR"]}')
         fitsio.write(str(output_file), out, hdr, overwrite=True)
         self._logger.info(f'Wrote stacked image to {output_file}')
         return res

@@ -721,8 +721,9 @@ extern "C" int apgpu_resample_stack_sigclip(const apgpu_stack_args *args, int64_
 {
     const char *who = "resample_stack_sigclip";
     if (!args || !args->frames || !affines || !lut) return fail(APGPU_EINVAL, "%s: NULL pointer argument", who);
-    if (args->flags & (APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX | APGPU_STACK_FRAME_PARAMS | APGPU_STACK_FRAME_LOCAL))
-        return fail(APGPU_EUNSUPPORTED, "%s: no Winsorized / min-max rejection and no frame parameters here (resample, then apgpu_stack_sigclip "
+    if (args->flags & (APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX | APGPU_STACK_REJECT_ESD | APGPU_STACK_FRAME_PARAMS |
+                       APGPU_STACK_FRAME_LOCAL))
+        return fail(APGPU_EUNSUPPORTED, "%s: no Winsorized / min-max / ESD rejection and no frame parameters here (resample, then apgpu_stack_sigclip "
                     "with the rule)", who);
     if (args->dtype != APGPU_F32) return fail(APGPU_EUNSUPPORTED, "%s: float32 frames", who);
     const int N = args->n_frames;

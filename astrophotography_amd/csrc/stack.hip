@@ -9,6 +9,8 @@ namespace apgpu_stack {
 int launch_big(const StackParams &prm, bool u16, bool calib, bool median_only, hipStream_t st, char *describe);   // stack_big.hip
 bool chunks_eligible(const StackParams &prm, bool median_only);                                                  // stack_chunks.hip
 int launch_reject(const apgpu_stack_args *args, hipStream_t st, char *describe);                                 // stack_reject.hip
+int launch_esd_f32(const apgpu_stack_args *args, hipStream_t st, char *describe);                                // stack_esd.hip, once
+int launch_esd_u16(const apgpu_stack_args *args, hipStream_t st, char *describe);                                // per raw dtype
 }
 
 namespace {
@@ -82,7 +84,9 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
     const bool calib = args->bias != nullptr;
     if (calib && (!args->dark || !args->exp_ratio))
         return fail(APGPU_EINVAL, "stack: fused calibration needs bias, dark and exp_ratio");
-    constexpr int kReject = APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX;
+    constexpr int kReject = APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX | APGPU_STACK_REJECT_ESD;
+    if ((args->flags & APGPU_STACK_REJECT_ESD) && median_only)
+        return fail(APGPU_EUNSUPPORTED, "stack_median: APGPU_STACK_REJECT_ESD is a rule of apgpu_stack_sigclip");
     if ((args->flags & APGPU_STACK_FRAME_PARAMS) && (median_only || !(args->flags & kReject)))
         return fail(APGPU_EUNSUPPORTED, "stack: APGPU_STACK_FRAME_PARAMS is served by the rejection rules only (APGPU_STACK_REJECT_WINSORIZED "
                     "or APGPU_STACK_REJECT_MINMAX of apgpu_stack_sigclip)");
@@ -91,20 +95,40 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
                     "or APGPU_STACK_REJECT_MINMAX of apgpu_stack_sigclip)");
     if (!median_only && (args->flags & kReject)) {
         // Winsorized clipping / min-max rejection (stack_reject.hip): one launch, no workspace - `workspace` is not looked at
-        // (with APGPU_STACK_FRAME_LOCAL it is the descriptor of the meshes, on the host)
+        // (with APGPU_STACK_FRAME_LOCAL it is the descriptor of the meshes, on the host).  The generalized ESD test
+        // (stack_esd.hip): `workspace` is its descriptor on the host, which names the table and, with the bit, the meshes.
+        const bool esd_rule = (args->flags & APGPU_STACK_REJECT_ESD) != 0;
+        const apgpu_stack_local *loc = nullptr;
         constexpr int kNoEffect = APGPU_STACK_EXACT_MOMENTS | APGPU_STACK_MOMENTS_MEAN | APGPU_STACK_SINGLE_KERNEL;
         if (args->flags & ~(kReject | kNoEffect | APGPU_STACK_NONFINITE_UNCLIPPED | APGPU_STACK_FRAME_PARAMS | APGPU_STACK_FRAME_LOCAL))
             return fail(APGPU_EINVAL, "stack: unknown flags 0x%x", args->flags);
+        if (esd_rule) {
+            if (args->flags & (APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX))
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_REJECT_WINSORIZED, APGPU_STACK_REJECT_MINMAX and APGPU_STACK_REJECT_ESD exclude each other");
+            if (!args->workspace || args->workspace_bytes != sizeof(apgpu_stack_esd))
+                return fail(APGPU_EINVAL, "stack: APGPU_STACK_REJECT_ESD needs workspace = a host apgpu_stack_esd and workspace_bytes = %zu",
+                            sizeof(apgpu_stack_esd));
+            const apgpu_stack_esd *esd = static_cast<const apgpu_stack_esd *>(args->workspace);
+            if (!esd->lambda) return fail(APGPU_EINVAL, "stack: apgpu_stack_esd.lambda is NULL");
+            if (esd->max_outliers < 1 || esd->max_outliers > 64)
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_esd.max_outliers = %d (1 .. 64)", esd->max_outliers);
+            if (esd->reserved != 0) return fail(APGPU_EINVAL, "stack: apgpu_stack_esd.reserved = %d must be 0", esd->reserved);
+            if ((esd->local != nullptr) != ((args->flags & APGPU_STACK_FRAME_LOCAL) != 0))
+                return fail(APGPU_EINVAL, "stack: apgpu_stack_esd.local must be non-NULL with APGPU_STACK_FRAME_LOCAL and NULL without");
+            loc = esd->local;
+        }
         if (args->flags & APGPU_STACK_FRAME_LOCAL) {
             if (args->flags & APGPU_STACK_FRAME_PARAMS)
                 return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL and APGPU_STACK_FRAME_PARAMS exclude each other");
             if (args->bias || args->dark || args->nflat || args->pedestal || args->exp_ratio)
                 return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL excludes the fused calibration and the frame parameters (bias, dark, "
                             "nflat, pedestal and exp_ratio must be NULL)");
-            if (!args->workspace || args->workspace_bytes != sizeof(apgpu_stack_local))
-                return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL needs workspace = a host apgpu_stack_local and workspace_bytes = %zu",
-                            sizeof(apgpu_stack_local));
-            const apgpu_stack_local *loc = static_cast<const apgpu_stack_local *>(args->workspace);
+            if (!esd_rule) {
+                if (!args->workspace || args->workspace_bytes != sizeof(apgpu_stack_local))
+                    return fail(APGPU_EINVAL, "stack: APGPU_STACK_FRAME_LOCAL needs workspace = a host apgpu_stack_local and workspace_bytes = %zu",
+                                sizeof(apgpu_stack_local));
+                loc = static_cast<const apgpu_stack_local *>(args->workspace);
+            }
             constexpr int64_t kMaxSide = 0x3fffffff;
             if (loc->width < 1 || loc->width > kMaxSide || args->n_pixels % loc->width != 0)
                 return fail(APGPU_EINVAL, "stack: apgpu_stack_local.width = %lld must be 1 .. 2^30 - 1 and divide n_pixels = %lld",
@@ -125,7 +149,7 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
                 return fail(APGPU_EINVAL, "stack: unknown flags 0x%x for a call without exp_ratio: APGPU_STACK_FRAME_PARAMS needs exp_ratio = "
                             "float32 [3][n_frames] (scale, offset, weight)", args->flags);
         }
-        if ((args->flags & kReject) == kReject)
+        if ((args->flags & kReject) == (APGPU_STACK_REJECT_WINSORIZED | APGPU_STACK_REJECT_MINMAX))
             return fail(APGPU_EINVAL, "stack: APGPU_STACK_REJECT_WINSORIZED and APGPU_STACK_REJECT_MINMAX exclude each other");
         if (args->flags & APGPU_STACK_NONFINITE_UNCLIPPED)
             return fail(APGPU_EINVAL, "stack: APGPU_STACK_NONFINITE_UNCLIPPED does not go with a rejection rule");
@@ -135,6 +159,12 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
             const double lo = args->sigma_lower, hi = args->sigma_upper;
             if (!(lo >= 0.0 && lo <= 127.0 && hi >= 0.0 && hi <= 127.0) || lo != (double)(int)lo || hi != (double)(int)hi)
                 return fail(APGPU_EINVAL, "stack: min/max rejection drops nlow = sigma_lower and nhigh = sigma_upper values, whole numbers in 0 .. 127");
+        } else if (esd_rule) {
+            const double frac = args->sigma_lower, relax = args->sigma_upper;
+            if (!(frac >= 0.0 && frac <= 0.5))
+                return fail(APGPU_EINVAL, "stack: the ESD test takes frac = sigma_lower, the largest fraction of outliers, in 0 .. 0.5");
+            if (!(relax >= 1.0 && relax < __builtin_inf()))
+                return fail(APGPU_EINVAL, "stack: the ESD test takes relax = sigma_upper, the low relaxation, >= 1 and finite");
         } else {
             if (args->maxiters == 0) return fail(APGPU_EINVAL, "stack: maxiters must be >= 1 or < 0");
             if (!(args->sigma_lower >= 0.0) || !(args->sigma_upper >= 0.0))
@@ -147,6 +177,8 @@ int stack_dispatch(const apgpu_stack_args *args, bool median_only, void *stream,
                         "lives in registers)", args->n_frames, APGPU_STACK_REJECT_MAX);
         if (!args->mean && !args->std && !args->count && !args->mean_f64 && !args->std_f64)
             return fail(APGPU_EINVAL, "stack: no output requested");
+        if (esd_rule)
+            return args->dtype == APGPU_F32 ? launch_esd_f32(args, as_stream(stream), describe) : launch_esd_u16(args, as_stream(stream), describe);
         return launch_reject(args, as_stream(stream), describe);
     }
     if (!median_only) {

@@ -6,6 +6,8 @@ only owns device memory and streams here; every computation is a hand-written HI
 asynchronous on the current torch stream.
 """
 import ctypes as C
+import functools
+import math
 
 import numpy as np
 import torch
@@ -373,7 +375,8 @@ def stack_sigclip(frames, sigma=3.0, sigma_lower=None, sigma_upper=None, maxiter
 
 
 def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma_upper=None, maxiters=None, nlow=1, nhigh=1,
-                 calib=None, pixmask=None, outputs=('mean',), scale=None, offset=None, weights=None, box=None, row0=0):
+                 calib=None, pixmask=None, outputs=('mean',), scale=None, offset=None, weights=None, box=None, row0=0,
+                 esd_outliers=0.3, esd_significance=0.05, esd_low_relaxation=1.5, esd_table=None):
     """The rejection rules of small stacks (5 .. 30 registered light frames, where an outlier inflates the standard deviation
     a sigma clip judges it by), per pixel along N, at most _lib.STACK_REJECT_MAX (128) frames; include/apgpu.h has the definition.
 
@@ -381,6 +384,11 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
     Winsorized estimate - the column clamped to median +- 1.5 sig, sig = 1.134 std of that, repeated until it settles;
     maxiters rounds (None: until a round removes nothing).
     method 'minmax': the nlow lowest and the nhigh highest values of a column are dropped (ties: by frame index).
+    method 'esd': the generalized extreme Studentized deviate test (Rosner 1983), for a couple of dozen frames and more: at most
+    the fraction esd_outliers (0 .. 0.5) of a column's values are candidates, taken one at a time from its two ends (a low one's
+    deviation divided by esd_low_relaxation >= 1), and the largest prefix of removals significant at level esd_significance
+    goes - a clean column loses a value with about that probability.  esd_table: the critical values, float64
+    [N + 1, max_outliers] (default: esd_lambda(N, esd_outliers, esd_significance)).
     calib / pixmask: as stack_sigclip.  outputs: any of 'mean', 'std', 'count' (float32 / int32 planes), 'mean_f64', 'std_f64'
     -> dict of device tensors; the statistics are numpy's of the survivors in frame order, the float32 planes their roundings.
     scale / offset / weights (APGPU_STACK_FRAME_PARAMS; all None: not used): one value per frame, missing ones 1 / 0 / 1.  The
@@ -396,8 +404,8 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
         loc = _frame_local(frames, scale, offset, weights, box, row0, calib)
     else:
         fp = _frame_params(frames, scale, offset, weights, calib)
-    if method not in ('winsorized', 'minmax'):
-        raise ValueError("method must be 'winsorized' or 'minmax', not %r" % (method,))
+    if method not in ('winsorized', 'minmax', 'esd'):
+        raise ValueError("method must be 'winsorized', 'minmax' or 'esd', not %r" % (method,))
     bad = [k for k in outputs if k not in ('mean', 'std', 'count', 'mean_f64', 'std_f64')]
     if bad or not outputs:
         raise ValueError('outputs of stack_reject are mean, std, count, mean_f64, std_f64; got %r' % (tuple(outputs),))
@@ -410,6 +418,20 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
             if isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= 127:
                 raise ValueError('%s must be a whole number in 0 .. 127, got %r' % (nm, c))
         lo, hi, mi = float(int(nlow)), float(int(nhigh)), 1
+    elif method == 'esd':
+        lo, hi, mi = float(esd_outliers), float(esd_low_relaxation), 1
+        if not 0.0 <= lo <= 0.5:
+            raise ValueError('esd_outliers is the largest fraction of outliers, 0 .. 0.5, got %r' % (esd_outliers,))
+        if not (hi >= 1.0 and np.isfinite(hi)):
+            raise ValueError('esd_low_relaxation must be >= 1 and finite, got %r' % (esd_low_relaxation,))
+        if esd_table is None:
+            esd_table = esd_lambda(frames.shape[0], lo, esd_significance)
+        esd_table = np.ascontiguousarray(esd_table, dtype=np.float64)
+        if esd_table.ndim != 2 or esd_table.shape[0] != frames.shape[0] + 1 or not 1 <= esd_table.shape[1] <= 64:
+            raise ValueError('esd_table must be float64 [N + 1, max_outliers] with N = %d and max_outliers in 1 .. 64, got shape %s'
+                             % (frames.shape[0], esd_table.shape))
+        if np.isnan(esd_table).any():
+            raise ValueError('esd_table must not hold NaN')
     else:
         lo = float(sigma if sigma_lower is None else sigma_lower)
         hi = float(sigma if sigma_upper is None else sigma_upper)
@@ -429,7 +451,7 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
         res[k] = torch.empty(shp, dtype={'count': torch.int32, 'mean_f64': torch.float64, 'std_f64': torch.float64}.get(k, torch.float32),
                              device=dev)
         setattr(a, k, res[k].data_ptr())
-    a.flags = _lib.STACK_REJECT_WINSORIZED if method == 'winsorized' else _lib.STACK_REJECT_MINMAX
+    a.flags = {'winsorized': _lib.STACK_REJECT_WINSORIZED, 'minmax': _lib.STACK_REJECT_MINMAX, 'esd': _lib.STACK_REJECT_ESD}[method]
     if fp is not None:
         block = torch.from_numpy(fp).to(dev)                 # float32 [3, N]: scale, offset, weight
         keep.append(block)
@@ -449,8 +471,117 @@ def stack_reject(frames, method='winsorized', sigma=3.0, sigma_lower=None, sigma
         keep.append(d)
         a.workspace, a.workspace_bytes = C.addressof(d), C.sizeof(d)
         a.flags |= _lib.STACK_FRAME_LOCAL
+    if method == 'esd':
+        # the table goes up once; the descriptor lives on the host until the call has returned and names the meshes' one
+        e = _lib.StackEsd()
+        t = torch.from_numpy(esd_table).to(dev)
+        keep.append(t)
+        e.lambda_, e.max_outliers, e.reserved = t.data_ptr(), esd_table.shape[1], 0
+        e.local = C.addressof(d) if loc is not None else None
+        keep.append(e)
+        a.workspace, a.workspace_bytes = C.addressof(e), C.sizeof(e)
     check(lib.apgpu_stack_sigclip(C.byref(a), _stream()))
     return res
+
+
+def _betacf(a, b, x):
+    """The continued fraction of the incomplete beta function (modified Lentz), to the last bits of float64."""
+    tiny = 1e-300
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c, d = 1.0, 1.0 - qab * x / qap
+    d = 1.0 / (d if abs(d) > tiny else tiny)
+    h = d
+    for m in range(1, 1000):
+        m2 = 2 * m
+        aa = m * (b - m) * x / ((qam + m2) * (a + m2))
+        d = 1.0 + aa * d
+        c = 1.0 + aa / c
+        d = 1.0 / (d if abs(d) > tiny else tiny)
+        c = c if abs(c) > tiny else tiny
+        h *= d * c
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))
+        d = 1.0 + aa * d
+        c = 1.0 + aa / c
+        d = 1.0 / (d if abs(d) > tiny else tiny)
+        c = c if abs(c) > tiny else tiny
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return h
+
+
+def _betainc(a, b, x):
+    """The regularized incomplete beta function I_x(a, b), 0 <= x <= 1."""
+    if x <= 0.0:
+        return 0.0
+    if x >= 1.0:
+        return 1.0
+    bt = math.exp(math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b) + a * math.log(x) + b * math.log1p(-x))
+    if x < (a + 1.0) / (a + b + 2.0):
+        return bt * _betacf(a, b, x) / a
+    return 1.0 - bt * _betacf(b, a, 1.0 - x) / b
+
+
+def _student_t_upper(q, df):
+    """t > 0 with P(T > t) = q for Student's t with df degrees of freedom, 0 < q < 0.5: the upper tail is
+    I_x(df / 2, 1 / 2) / 2 at x = df / (df + t^2); a bisection brackets the root, Newton steps on log(tail) finish it."""
+    def tail(t):
+        return 0.5 * _betainc(0.5 * df, 0.5, df / (df + t * t))
+    lo, hi = 0.0, 1.0
+    while tail(hi) > q:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(12):
+        mid = 0.5 * (lo + hi)
+        if tail(mid) > q:
+            lo = mid
+        else:
+            hi = mid
+    t = 0.5 * (lo + hi)
+    lognorm = math.lgamma(0.5 * (df + 1.0)) - math.lgamma(0.5 * df) - 0.5 * math.log(df * math.pi)
+    for _ in range(50):
+        sf = tail(t)
+        pdf = math.exp(lognorm - 0.5 * (df + 1.0) * math.log1p(t * t / df))
+        step = sf * math.log(sf / q) / pdf                   # Newton on log(tail(t)) - log(q)
+        t_new = min(max(t + step, lo), hi)
+        if abs(t_new - t) <= 4e-16 * t:
+            t = t_new
+            break
+        t = t_new
+    return t
+
+
+@functools.lru_cache(maxsize=None)
+def _esd_critical(m, alpha):
+    """The critical value of one ESD step with m values left: p = 1 - alpha / (2 m), t the p-quantile of Student's t with
+    m - 2 degrees of freedom, lambda = (m - 1) t / sqrt((m - 2 + t^2) m)."""
+    t = _student_t_upper(alpha / (2.0 * m), m - 2.0)
+    return (m - 1.0) * t / math.sqrt((m - 2.0 + t * t) * m)
+
+
+def esd_lambda(n_frames, frac=0.3, alpha=0.05, max_outliers=None):
+    """The table of critical values the ESD rule of stack_reject takes (include/apgpu.h, APGPU_STACK_REJECT_ESD): float64
+    [n_frames + 1, max_outliers], row n for a column of n finite values, entry i for step i - m = n - i values left.  Entries
+    with i >= K_n = min(floor(frac n), n - 3, max_outliers) and the rows n < 4 hold +inf.  max_outliers: default the largest
+    K_n (at least 1), at most 64.  Plain Python: the package does not depend on SciPy."""
+    n_frames, frac, alpha = int(n_frames), float(frac), float(alpha)
+    if n_frames < 1:
+        raise ValueError('n_frames must be >= 1')
+    if not 0.0 <= frac <= 0.5:
+        raise ValueError('frac is the largest fraction of outliers, 0 .. 0.5, got %r' % (frac,))
+    if not 0.0 < alpha < 1.0:
+        raise ValueError('alpha (the significance level) must lie in (0, 1), got %r' % (alpha,))
+    kn = [min(int(np.floor(frac * n)), n - 3) for n in range(n_frames + 1)]
+    if max_outliers is None:
+        max_outliers = min(max(max(kn), 1), 64)
+    max_outliers = int(max_outliers)
+    if not 1 <= max_outliers <= 64:
+        raise ValueError('max_outliers must lie in 1 .. 64, got %r' % (max_outliers,))
+    lam = np.full((n_frames + 1, max_outliers), np.inf)
+    for n in range(4, n_frames + 1):
+        for i in range(min(kn[n], max_outliers)):
+            lam[n, i] = _esd_critical(n - i, alpha)
+    return lam
 
 
 def _box_pair(box):
@@ -790,10 +921,10 @@ def combine_f64(frames, sigma_lower=5.0, sigma_upper=5.0, maxiters=1, cenfunc='m
 def stack_kernel_name(n_frames, dtype='f32', calibrated=True, outputs=('mean',), median_only=False, stdfunc='std',
                       moments_mean_only=False, exact=False, maxiters=5, rejection=None):
     """Name of the kernel variant the library dispatches for such a stack call (apgpu_stack_kernel_name): what the
-    bench line and the profiles call the dominant kernel.  Needs no device.  rejection: None, 'winsorized' or 'minmax'
+    bench line and the profiles call the dominant kernel.  Needs no device.  rejection: None, 'winsorized', 'minmax' or 'esd'
     (stack_reject)."""
-    if rejection not in (None, 'winsorized', 'minmax'):
-        raise ValueError("rejection must be None, 'winsorized' or 'minmax'")
+    if rejection not in (None, 'winsorized', 'minmax', 'esd'):
+        raise ValueError("rejection must be None, 'winsorized', 'minmax' or 'esd'")
     lib = _lib.load()
     a = StackArgs()
     a.frames = 0x1000                                     # placeholders: aligned, never dereferenced by the query
@@ -816,9 +947,14 @@ def stack_kernel_name(n_frames, dtype='f32', calibrated=True, outputs=('mean',),
             setattr(a, k, 0x1000)
     a.flags = (_lib.STACK_EXACT_MOMENTS if exact else 0) | (_lib.STACK_MOMENTS_MEAN if moments_mean_only else 0)
     if rejection is not None:
-        a.flags |= _lib.STACK_REJECT_WINSORIZED if rejection == 'winsorized' else _lib.STACK_REJECT_MINMAX
+        a.flags |= {'winsorized': _lib.STACK_REJECT_WINSORIZED, 'minmax': _lib.STACK_REJECT_MINMAX, 'esd': _lib.STACK_REJECT_ESD}[rejection]
         if rejection == 'minmax':
             a.sigma_lower = a.sigma_upper = 1.0
+        if rejection == 'esd':
+            a.sigma_lower, a.sigma_upper = 0.3, 1.5
+            e = _lib.StackEsd()
+            e.lambda_, e.max_outliers = 0x1000, 1
+            a.workspace, a.workspace_bytes = C.addressof(e), C.sizeof(e)
     buf = C.create_string_buffer(256)
     check(lib.apgpu_stack_kernel_name(C.byref(a), int(bool(median_only)), buf, 256))
     return buf.value.decode()
@@ -1438,16 +1574,20 @@ def background_weights(frames, fscale=None, sigma=3.0, maxiters=5):
     return 1.0 / (fs * sd) ** 2
 
 
-COADD_COMBINE = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX')
+COADD_COMBINE = ('MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX', 'ESD')
+COADD_REJECT = ('WINSORIZED', 'MINMAX', 'ESD')                 # the rules of stack_reject: normalize, weighting and norm_box go with them
 
 
 def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDIAN', sigma=3.0, maxiters=5, n_phases=1024,
           conserve_flux=False, oversampling=1, weights=None, fine_affines=None, fused=False, nlow=1, nhigh=1,
-          normalize='none', reference=0, weighting=None, norm_box=None):
+          normalize='none', reference=0, weighting=None, norm_box=None, esd_outliers=0.3, esd_significance=0.05,
+          esd_low_relaxation=1.5):
     """Resample + combine: SWarp's COMBINE_TYPE MEDIAN / AVERAGE / WEIGHTED / SUM (resample_all.sh:60-73 add modes) plus
     CLIPPED (sigma-clipped mean, median-centred), WINSORIZED (Winsorized sigma clip at `sigma`, `maxiters` rounds) and MINMAX
     (the nlow lowest and nhigh highest values of a pixel dropped) - the two rules for stacks of few frames (stack_reject; up to
-    128 frames; fused does not apply); oversampling = SWarp's OVERSAMPLING.  WEIGHTED takes one weight per frame
+    128 frames; fused does not apply) - and ESD, the generalized ESD test for a couple of dozen frames and more (esd_outliers,
+    esd_significance, esd_low_relaxation: stack_reject; normalize, weighting and norm_box go with it as with WINSORIZED);
+    oversampling = SWarp's OVERSAMPLING.  WEIGHTED takes one weight per frame
     (default: background_weights).  Returns dict(image, count[, weight]) - count = frames contributing, weight = the sum
     of their weights (WEIGHTED only).
     fused=True (CLIPPED / AVERAGE, up to 16 frames, oversampling 1): one launch, no [N, h, w] slab of resampled frames in
@@ -1474,18 +1614,18 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
         raise ValueError('normalize must be one of ' + ', '.join(NORMALIZE_MODES) + ', not %r' % (normalize,))
     if weighting not in (None, 'noise'):
         raise ValueError("weighting must be None or 'noise', not %r" % (weighting,))
-    if weighting is not None and combine not in ('WINSORIZED', 'MINMAX'):
+    if weighting is not None and combine not in COADD_REJECT:
         raise ValueError('weighting goes with combine WINSORIZED and MINMAX only (WEIGHTED takes weights), not with %s' % combine)
     normed = normalize != 'none' or weighting is not None
     if norm_box is not None:
         norm_box = _box_pair(norm_box)
-        if combine not in ('WINSORIZED', 'MINMAX'):
+        if combine not in COADD_REJECT:
             raise ValueError('norm_box (the local normalisation) goes with combine WINSORIZED and MINMAX only, not with %s '
                              '(MINMAX with nlow = nhigh = 0 is the normalised, weighted average)' % combine)
         normed = True
     if fused and normed:
         raise ValueError('fused=True does not go with a normalisation: the statistics are taken on the resampled slab')
-    if combine in ('WINSORIZED', 'MINMAX') and frames.dim() == 3 and frames.shape[0] > _lib.STACK_REJECT_MAX:
+    if combine in COADD_REJECT and frames.dim() == 3 and frames.shape[0] > _lib.STACK_REJECT_MAX:
         raise ValueError('combine %s takes at most %d frames (STACK_REJECT_MAX), got %d' % (combine, _lib.STACK_REJECT_MAX, frames.shape[0]))
     if fused and int(oversampling) == 1 and combine in ('CLIPPED', 'AVERAGE') and frames.dim() == 3 and frames.shape[0] <= 16:
         kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'CLIPPED' else dict(sigma=1e30, maxiters=1, cenfunc='mean')
@@ -1498,20 +1638,23 @@ def coadd(frames, affines, fscale=None, mask=None, out_shape=None, combine='MEDI
     else:
         res, _ = resample_affine(frames, affines, fscale=fscale, mask=mask, out_shape=out_shape, n_phases=n_phases, weight=False,
                                  conserve_flux=conserve_flux)
+    rule_kw = {'WINSORIZED': dict(sigma=sigma, maxiters=maxiters), 'MINMAX': dict(nlow=nlow, nhigh=nhigh),
+               'ESD': dict(esd_outliers=esd_outliers, esd_significance=esd_significance, esd_low_relaxation=esd_low_relaxation)}.get(combine)
+    if combine == 'ESD' and not normed:
+        r = stack_reject(res, 'esd', outputs=('mean', 'count'), **rule_kw)
+        return dict(image=r['mean'], count=r['count'])
     if norm_box is not None:
         if res.dim() != 3:
             raise ValueError('norm_box needs frames [N, H, W]')
         a, b, w = local_normalization(local_stats(res, norm_box, sigma=3.0, maxiters=5), normalize, reference=reference,
                                       weighting=weighting, box=norm_box)
-        kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'WINSORIZED' else dict(nlow=nlow, nhigh=nhigh)
-        r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, box=norm_box, **kw)
+        r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, box=norm_box, **rule_kw)
         return dict(image=r['mean'], count=r['count'], scale=a, offset=b, norm_weights=w, norm_box=norm_box)
     if normed:
         a, b, w = frame_normalization(frame_stats(res, sigma=3.0, maxiters=5), normalize, reference=reference, weighting=weighting)
         extra = dict(scale=a, offset=b, norm_weights=w)
-        if combine in ('WINSORIZED', 'MINMAX'):
-            kw = dict(sigma=sigma, maxiters=maxiters) if combine == 'WINSORIZED' else dict(nlow=nlow, nhigh=nhigh)
-            r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, **kw)
+        if combine in COADD_REJECT:
+            r = stack_reject(res, combine.lower(), outputs=('mean', 'count'), scale=a, offset=b, weights=w, **rule_kw)
             return dict(image=r['mean'], count=r['count'], **extra)
         # the other rules: the same float32 map on the slab in place - multiply, then add: two roundings
         bc = (res.shape[0],) + (1,) * (res.dim() - 1)

@@ -19,9 +19,10 @@ def command_line_opts(argv):
                         help='Per-file 2x3 affine transforms. Default: register through the TAN WCS of the file headers.')
     parser.add_argument('--center', default=None, metavar='RA,DEC', help='Output tangent point in degrees (WCS mode).')
     parser.add_argument('--pixelscale', default=None, type=float, metavar='ARCSEC', help='Output pixel scale (WCS mode).')
-    parser.add_argument('--combine', default='MEDIAN', choices=['MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX'],
+    parser.add_argument('--combine', default='MEDIAN', choices=['MEDIAN', 'AVERAGE', 'WEIGHTED', 'SUM', 'CLIPPED', 'WINSORIZED', 'MINMAX', 'ESD'],
                         help='Combine type (resample_all.sh add modes 0/1/2 = MEDIAN/WEIGHTED/SUM); WINSORIZED and MINMAX reject '
-                             'outliers in stacks of few frames (at most 128). Default: MEDIAN')
+                             'outliers in stacks of few frames, ESD (the generalized ESD test) in stacks of a couple of dozen and more (at most 128). '
+                             'Default: MEDIAN')
     parser.add_argument('--weight_image', default=None, metavar='WEIGHTS.FITS', help='Optional output weight image.')
     parser.add_argument('--badpix', default=None, metavar='BADPIX.FITS', help='Optional bad pixel mask shared by the inputs.')
     parser.add_argument('--image_size', default=None, metavar='NX,NY', help='Output size (default: input size).')
@@ -33,16 +34,21 @@ def command_line_opts(argv):
     parser.add_argument('--maxiters', default=5, type=int, metavar='N', help='CLIPPED and WINSORIZED; -1 = until convergence.')
     parser.add_argument('--nlow', default=1, type=int, metavar='N', help='MINMAX: lowest values dropped per pixel. Default: 1')
     parser.add_argument('--nhigh', default=1, type=int, metavar='N', help='MINMAX: highest values dropped per pixel. Default: 1')
+    parser.add_argument('--esd_outliers', default=0.3, type=float, metavar='FRACTION',
+                        help='ESD: the largest fraction of a pixel\'s values that may be outliers, 0 .. 0.5. Default: 0.3')
+    parser.add_argument('--esd_significance', default=0.05, type=float, metavar='ALPHA', help='ESD: significance level of the test. Default: 0.05')
+    parser.add_argument('--esd_low_relaxation', default=1.5, type=float, metavar='FACTOR',
+                        help='ESD: a low value\'s deviation is divided by this before it is tested (>= 1). Default: 1.5')
     parser.add_argument('--normalize', default='none', choices=['none', 'additive', 'multiplicative', 'additive+scaling'],
                         help='Bring the resampled frames to the level of the reference frame before they are combined: by an offset '
                              '(sky level), a factor (transparency) or scale and offset (noise and sky). Default: none')
     parser.add_argument('--reference', default='0', metavar='FILE_OR_INDEX',
                         help='The frame the others are normalised to: one of the input files or its index. Default: 0')
     parser.add_argument('--weighting', default='none', choices=['none', 'noise'],
-                        help='WINSORIZED and MINMAX: average the surviving values with inverse-variance weights of the '
+                        help='WINSORIZED, MINMAX and ESD: average the surviving values with inverse-variance weights of the '
                              'normalised frames. Default: none')
     parser.add_argument('--norm_box', default=None, type=int, metavar='PIXELS',
-                        help='WINSORIZED and MINMAX: normalise LOCALLY - the statistics are taken per box of PIXELS x PIXELS and scale and '
+                        help='WINSORIZED, MINMAX and ESD: normalise LOCALLY - the statistics are taken per box of PIXELS x PIXELS and scale and '
                              'offset are interpolated at every pixel, for frames whose sky differs in shape (moon, light dome, '
                              'meridian flip). Default: one scale and one offset per frame')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
@@ -73,7 +79,8 @@ def main(args=None):
         out_shape = (ny, nx)
     rs = ApResample(p.loglevel, combine=p.combine, sigma=p.sigma, maxiters=None if p.maxiters < 0 else p.maxiters,
                     oversampling=p.oversampling, gain_keyword=p.gain_keyword, nlow=p.nlow, nhigh=p.nhigh, normalize=p.normalize, reference=p.reference,
-                    weighting=None if p.weighting == 'none' else p.weighting, norm_box=p.norm_box)
+                    weighting=None if p.weighting == 'none' else p.weighting, norm_box=p.norm_box,
+                    esd_outliers=p.esd_outliers, esd_significance=p.esd_significance, esd_low_relaxation=p.esd_low_relaxation)
     center = None
     if p.center:
         center = tuple(float(v) for v in p.center.split(','))

@@ -275,6 +275,48 @@ typedef struct apgpu_stack_local {
     const float *weight;            /* device float32 [n_frames], or NULL = 1 */
 } apgpu_stack_local;
 
+/* APGPU_STACK_REJECT_ESD: the generalized extreme Studentized deviate test (Rosner 1983) as a third rejection rule, for stacks of a
+ * couple of dozen frames and more.  The caller states the largest fraction of a column that may be outliers; candidates are taken
+ * one at a time from the column's two ends, and the largest prefix of removals that is significant is what goes - two equal
+ * outliers cannot mask each other, and a clean column loses a value with probability about alpha, not alpha per value.
+ * Mutually exclusive with APGPU_STACK_REJECT_WINSORIZED and APGPU_STACK_REJECT_MINMAX (APGPU_EINVAL); everything said for those
+ * bits holds: one launch, float64 arithmetic, n_frames <= APGPU_STACK_REJECT_MAX, outputs mean / std / count / mean_f64 / std_f64
+ * (`moments` or `median`: APGPU_EUNSUPPORTED), center APGPU_CENTER_MEDIAN and dev APGPU_DEV_STD, APGPU_STACK_NONFINITE_UNCLIPPED is
+ * APGPU_EINVAL, the no-effect bits are accepted, both dtypes, the fused calibration, pixmask and frame_stride work,
+ * APGPU_STACK_FRAME_PARAMS and APGPU_STACK_FRAME_LOCAL combine with it; the median entry point and the fused resample + clip do
+ * not serve it (APGPU_EUNSUPPORTED).
+ *   sigma_lower = frac, the largest fraction of outliers, 0 .. 0.5; sigma_upper = relax, the low relaxation (a low candidate's
+ *   deviation is divided by it: dark outliers are rarer than bright ones), >= 1 and finite; else APGPU_EINVAL.  maxiters unused.
+ *   `workspace` is a HOST pointer to an apgpu_stack_esd and workspace_bytes its size; the library reads it on the host during the
+ *   call.  lambda: the critical values on the DEVICE, float64 [n_frames + 1][max_outliers], lambda[n * max_outliers + i] for step
+ *   i of a column of n finite values (the caller guarantees: no NaN; +inf = never significant).  With APGPU_STACK_FRAME_LOCAL the
+ *   mesh descriptor is `local` (checked as described there).  APGPU_EINVAL: lambda NULL, max_outliers outside 1 .. 64,
+ *   reserved != 0, local non-NULL without the bit or NULL with it.
+ * Definition (no contraction: every operation rounds on its own).  Per pixel, S = the finite values of the column after the
+ * calibration or the frame map, in float64, n = len(S); a masked pixel or an empty S gives NaN (0x7fc00000) and count 0.
+ *     K = min(floor(frac * n), n - 3, max_outliers)        (frac * n: one float64 product; K <= 0: nothing is removed)
+ *     y = S ordered by (order-preserving key of the value: -0 below +0, then frame index);  lo, hi = 0, n;  L = H = 0
+ *     for i in 0 .. K-1:
+ *         w = y[lo:hi];  m = hi - lo
+ *         mean = np.add.reduce(w) / m;  d = w - mean;  sd = np.sqrt(np.add.reduce(d * d) / (m - 1))
+ *         if not (sd > 0): break
+ *         dl = (mean - w[0]) / relax;  dh = w[m-1] - mean
+ *         if dh >= dl: R = dh / sd; hi -= 1     else: R = dl / sd; lo += 1
+ *         if R > lambda[n][i]: L, H = lo, n - hi
+ *     survivors = the APGPU_STACK_REJECT_MINMAX rule with nlow = L, nhigh = H on S (same ties)
+ *   count, mean_f64, std_f64 and the weighted mean under APGPU_STACK_FRAME_PARAMS / APGPU_STACK_FRAME_LOCAL are formed word for word
+ *   as for APGPU_STACK_REJECT_MINMAX.
+ * The table (ops.esd_lambda computes it on the host): with m = n - i values left, p = 1 - alpha / (2 m) and t the p-quantile of
+ * Student's t with m - 2 degrees of freedom, lambda = (m - 1) t / sqrt((m - 2 + t^2) m); entries with i >= K_n and rows n < 4
+ * hold +inf. */
+#define APGPU_STACK_REJECT_ESD 256
+typedef struct apgpu_stack_esd {
+    const double *lambda;            /* device float64 [n_frames + 1][max_outliers]: lambda[n * max_outliers + i] */
+    int32_t max_outliers;            /* 1 .. 64 */
+    int32_t reserved;                /* 0 */
+    const apgpu_stack_local *local;  /* host; non-NULL iff APGPU_STACK_FRAME_LOCAL is set */
+} apgpu_stack_esd;
+
 /* The two-kernel scheme and its workspace.  A clipped stack of up to 128 frames (and the chunked kernel for 129 .. 512) with
  * lean outputs runs as a FAST kernel - the float32 fast path alone, four wavefronts per SIMD - followed by a REDO PASS of the
  * complete kernel over what the fast kernel could not finish: single pixels (unsure comparisons, non-finite values, masked
