@@ -36,6 +36,7 @@ STARLET_FIRST, STARLET_LAST = 1, 2                      # APGPU_STARLET_FIRST, A
 STARLET_FORM = {'auto': 0, 'tile': 1, 'direct': 2}      # APGPU_STARLET_FORM_*
 DRIZZLE_TILE_H, DRIZZLE_TILE_W = 4, 64                  # APGPU_DRIZZLE_TILE_H, APGPU_DRIZZLE_TILE_W
 DEMOSAIC_RCD_TILE_H, DEMOSAIC_RCD_TILE_W, DEMOSAIC_RCD_HALO = 32, 64, 10     # APGPU_DEMOSAIC_RCD_TILE_H, _TILE_W, _HALO
+POLY_MAX_DEGREE = 5                                     # APGPU_POLY_MAX_DEGREE
 
 
 class ApGpuError(RuntimeError):
@@ -195,6 +196,14 @@ SIGNATURES = {
                                     C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'apgpu_drizzle_reject_u8': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'apgpu_nearest_match_poly': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                           C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_poly_tile_affines': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int64, C.c_int64,
+                                          C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_drizzle_tiles_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                          C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'apgpu_drizzle_reject_tiles_u8': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -16,9 +16,12 @@ pixel), DRIZPIXF (pixfrac), DRIZKERN = 'TURBO', DRIZNREJ (pixels flagged by the 
 Rejection in CFA mode is refused (ValueError): its reference would have to be built per colour from a quarter of the pixels; flag the
 mosaics beforehand (ap_fix_cosmic_rays) or pass frame masks to drizzle().
 
-Out of scope: the exact polygon ("square") kernel and the point, Gaussian and Lanczos drop kernels; per-tile affines / TAN-WCS
-registration; per-pixel input weight maps; a second rejection pass with tighter thresholds; multi-GPU sharding; more than one
-transform per frame.
+Lens distortion (DESIGN 4.3e'): with `maps` (one distortion.PolyMap per frame, what ap_register --model polyN writes) the drizzle,
+the median reference and the rejection take one transform per 16 x 64 tile - of the output, of the scale-1 grid and of the input
+frame - instead of one per frame; footprint, weight and flux factor are then each tile's own.
+
+Out of scope: the exact polygon ("square") kernel and the point, Gaussian and Lanczos drop kernels; TAN-WCS registration; per-pixel
+input weight maps; a second rejection pass with tighter thresholds; multi-GPU sharding.
 """
 from datetime import datetime, timezone
 from pathlib import Path
@@ -61,11 +64,13 @@ class ApDrizzle:
         self.gain_keyword = gain_keyword
 
     # -- tensors -----------------------------------------------------------------------------------------
-    def drizzle(self, frames, affines, fscale=None, weights=None, mask=None, frame_masks=None, out_shape=None, cfa=None, sigmas=None):
+    def drizzle(self, frames, affines, fscale=None, weights=None, mask=None, frame_masks=None, out_shape=None, cfa=None, sigmas=None,
+                maps=None, max_tile_error=0.01):
         """frames [N,H,W] float32 device tensor, affines one 2x3 transform per frame (reference pixel -> input pixel).  weights: None
         takes the constructor's weighting.  cfa: None or (pattern, channel).  With reject (not with cfa) the frames are first compared
         with their own median co-add on the scale-1 grid and the flags are added to frame_masks; sigmas: the frames' noise in
-        flux-scaled units (None: measured).
+        flux-scaled units (None: measured).  maps: one distortion.PolyMap per frame, used in place of `affines` through per-tile
+        transforms (ValueError when a tile's linearisation would cost more than max_tile_error input pixels).
 
         Returns dict(image, weight, rejected): rejected = flagged pixels per frame (numpy int64 [N]) or None."""
         import torch
@@ -73,6 +78,20 @@ class ApDrizzle:
         if frames.dim() == 2:
             frames = frames[None]
         N = frames.shape[0]
+        in_shape = tuple(frames.shape[1:])
+        co_affines = rej_affines = affines                               # what the median reference and the rejection take
+        if maps is not None:
+            maps = list(maps)
+            if len(maps) != N:
+                raise ValueError(f'{len(maps)} distortion maps given for {N} frames.')
+            shape = ops.drizzle_out_shape(in_shape, self.scale) if out_shape is None else out_shape
+            affines, est = ops.poly_tile_affines(maps, shape, scale=self.scale, max_tile_error=max_tile_error, composed=False,
+                                                 device=frames.device)
+            self._logger.info(f'Distortion maps of degree {maps[0].degree}: one transform per 16 x 64 output tile, linearisation error at '
+                              f'most {est:.2e} input pixels.')
+            if self.reject:
+                co_affines, _ = ops.poly_tile_affines(maps, in_shape, max_tile_error=max_tile_error, device=frames.device)
+                rej_affines = ops.poly_input_tile_affines(maps, in_shape)
         fs = np.ones(N) if fscale is None else np.broadcast_to(np.asarray(fscale, np.float64).reshape(-1), (N,))
         sd = None
         if weights is None and self.weighting == 'background' or self.reject and sigmas is None:
@@ -83,9 +102,8 @@ class ApDrizzle:
         if self.reject:
             if cfa is not None:
                 raise ValueError('Rejection is not available in CFA mode: flag the mosaics beforehand or pass frame_masks.')
-            in_shape = tuple(frames.shape[1:])
-            ref = ops.coadd(frames, affines, fscale=fs.astype(np.float32), mask=mask, out_shape=in_shape, combine='MEDIAN', conserve_flux=False)
-            flags = ops.drizzle_reject(frames, affines, ref['image'], 1.0, fscale=fs, sigmas=sd if sigmas is None else sigmas, k=self.k,
+            ref = ops.coadd(frames, co_affines, fscale=fs.astype(np.float32), mask=mask, out_shape=in_shape, combine='MEDIAN', conserve_flux=False)
+            flags = ops.drizzle_reject(frames, rej_affines, ref['image'], 1.0, fscale=fs, sigmas=sd if sigmas is None else sigmas, k=self.k,
                                        grow=self.grow)
             rejected = flags.reshape(N, -1).sum(1, dtype=torch.int64).cpu().numpy()
             for i, n in enumerate(rejected):
@@ -105,11 +123,13 @@ class ApDrizzle:
                 return float(hdr[kw])
         raise RuntimeError(f'Error, could not find EXPOSURE keyword in {fname}.')
 
-    def drizzle_files(self, input_files, affines, output_file, weight_file=None, mask_file=None, cfa=False, pattern=None, out_shape=None):
+    def drizzle_files(self, input_files, affines, output_file, weight_file=None, mask_file=None, cfa=False, pattern=None, out_shape=None,
+                      maps=None, max_tile_error=0.01):
         """Drizzles FITS files.  affines: one [a00, a01, a02, a10, a11, a12] per file (what ap_register writes).  Flux scale per
         file = 1 / EXPOSURE (or EXPTIME).  cfa: the files are Bayer mosaics; the pattern is `pattern` (RGGB, BGGR, GRBG, GBRG or four
         colour indices) or the first file's BAYERPAT shifted by XBAYROFF / YBAYROFF, and three files OUT_r.fits, OUT_g.fits, OUT_b.fits
-        are written (OUT = output_file without .fits), with weight maps W_r/_g/_b.fits when weight_file = W.fits is given.
+        are written (OUT = output_file without .fits), with weight maps W_r/_g/_b.fits when weight_file = W.fits is given.  maps: as
+        drizzle takes them.
         Returns the result of drizzle() (cfa: a list of three)."""
         import torch
         from .ApStack import _apply_pedestals
@@ -150,7 +170,7 @@ class ApDrizzle:
         results = []
         for channel, out_name, w_name in outputs:
             res = self.drizzle(slab, affines, fscale=np.asarray(fscale), mask=mask, out_shape=out_shape,
-                               cfa=None if channel is None else (pat, channel))
+                               cfa=None if channel is None else (pat, channel), maps=maps, max_tile_error=max_tile_error)
             results.append(res)
             nrej = 0 if res['rejected'] is None else int(res['rejected'].sum())
             hdr = hdrs[0].copy()

@@ -2,7 +2,8 @@
 astrometry.net through ApAstrometry, a network service that is out of scope here).
 
 The frames' brightness-ordered source lists (ApFindStars) are matched with the list of a reference frame by triangle
-similarity (Groth 1986; Valdes et al. 1995) and one affine per frame is fitted, in the convention ApResample.coadd,
+similarity (Groth 1986; Valdes et al. 1995) and one affine per frame is fitted - with model 'poly2' .. 'poly5' also a polynomial
+distortion map on top of it (DESIGN 4.3e': camera lenses, short refractors, two telescopes) -, in the convention ApResample.coadd,
 ops.resample_affine and ``ap_coadd --transforms`` use: ``x_frame = a0 x + a1 y + a2, y_frame = a3 x + a4 y + a5`` for (x, y)
 on the reference frame's grid, 0-based, integer = pixel centre.  The rule is DESIGN 4.3e; the triangle and neighbour searches
 are HIP kernels (csrc/register.hip), the fits a few float64 NumPy lines (ops.register_lists).
@@ -25,8 +26,8 @@ class ApRegister:
     """Register frames on a reference frame from their star lists."""
 
     def __init__(self, loglevel='INFO', K=40, eps=0.002, match_radius=3.0, model='affine', allow_mirror=False, min_side=5.0):
-        if model not in ('affine', 'similarity'):
-            raise ValueError(f"model must be 'affine' or 'similarity', got {model!r}.")
+        if model not in ('affine', 'similarity', 'poly2', 'poly3', 'poly4', 'poly5'):
+            raise ValueError(f"model must be 'affine', 'similarity' or 'poly2' .. 'poly5', got {model!r}.")
         self._loglevel = loglevel
         self._K = int(K)
         self._eps = float(eps)
@@ -74,6 +75,9 @@ class ApRegister:
                 self._logger.info('{}: {} seeds, {} matched, rms {:.3f} pix, rotation {:.4f} deg, scale {:.6f}, shift ({:.3f}, {:.3f})'
                                   .format(name, q['n_seed'], q['n_matched'], q['rms'], q['rotation_deg'], q['scale'], q['shift_x'],
                                           q['shift_y']))
+                if 'order' in q:
+                    self._logger.info('{}: polynomial of order {}, rms {:.3f} pix after {:.3f} pix of the affine'
+                                      .format(name, q['order'], q['rms'], q['rms_affine']))
             else:
                 self._logger.warning(f'{name}: not registered ({q["n_seed"]} seeds, {q["n_matched"]} matched).')
         return self._result
@@ -118,6 +122,8 @@ class ApRegister:
             a = r['coeffs'][f]
             q.update(rms=float(r['rms'][f]), rotation_deg=math.degrees(math.atan2(a[3] - a[1], a[0] + a[4])),
                      scale=math.sqrt(abs(a[0] * a[4] - a[1] * a[3])), shift_x=float(a[2]), shift_y=float(a[5]))
+            if 'order' in r:
+                q.update(order=int(r['order'][f]), rms_affine=float(r['rms_affine'][f]))
         return q
 
     def _failed(self):
@@ -132,13 +138,22 @@ class ApRegister:
             raise RuntimeError('Not registered: ' + ', '.join(self._failed()))
         return [[float(v) for v in r['coeffs'][f]] for f in range(len(self._names)) if r['ok'][f]]
 
+    def maps(self, skip_failed=False):
+        """The distortion maps (distortion.PolyMap, one degree, origin and scale) of the frames `affines` lists, in that order, with
+        a polynomial model; None with 'affine' or 'similarity'."""
+        r = self._need_result()
+        if self._failed() and not skip_failed:
+            raise RuntimeError('Not registered: ' + ', '.join(self._failed()))
+        return [m for m, ok in zip(r['maps'], r['ok']) if ok] if 'maps' in r else None
+
     def names(self, skip_failed=False):
         r = self._need_result()
         return [n for n, ok in zip(self._names, r['ok']) if ok or not skip_failed]
 
     def write_transforms(self, path, skip_failed=False):
         """Writes the YAML file ``ap_coadd --transforms`` reads: ``transforms:`` frame name -> 6 coefficients, plus
-        ``quality:`` frame name -> quality(f) (ap_coadd ignores it)."""
+        ``quality:`` frame name -> quality(f) (ap_coadd ignores it).  With a polynomial model also ``distortion:`` {origin, scale,
+        frames: frame name -> {order, x, y}} (distortion.to_document), which ap_coadd and ap_drizzle use in place of the affine."""
         import yaml
         r = self._need_result()
         if self._failed() and not skip_failed:
@@ -149,6 +164,9 @@ class ApRegister:
             raise RuntimeError('Two frames share a name: the transforms file is keyed by name.')
         doc = {'transforms': {n: [float(v) for v in r['coeffs'][f]] for f, n in enumerate(self._names) if r['ok'][f]},
                'quality': {n: self.quality(f) for f, n in enumerate(self._names)}}
+        if 'maps' in r:
+            from ..distortion import to_document
+            doc['distortion'] = to_document(r['maps'], r['order'], self._names)
         with open(path, 'w') as fh:
             yaml.safe_dump(doc, fh, sort_keys=False)
         self._logger.info(f'Wrote the transforms of {len(doc["transforms"])} frames to {path}')

@@ -7,7 +7,8 @@ weight-map output (:60-73, 108-118, 330-342).  ``ApResample`` keeps that contrac
 transform per frame (output pixel -> input pixel): Lanczos-3 resampling onto the common grid
 (``ops.resample_affine``), the flux scaling, the combine, and a weight image (= number of frames that
 contributed to each pixel).  Files that carry a TAN WCS (astrometry.net) are registered through the sky with one
-affine per 16 x 64 output tile (wcs.tile_affines); distortion polynomials (SIP / TPV) are not supported.
+affine per 16 x 64 output tile (wcs.tile_affines); SIP distortion polynomials of the inputs are followed (wcs.SipWcs), TPV is not
+supported, and the output grid is always pure TAN.
 """
 from datetime import datetime, timezone
 from pathlib import Path
@@ -117,12 +118,15 @@ class ApResample:
         raise RuntimeError(f'Error, could not find EXPOSURE keyword in {fname}.')
 
     def coadd_files(self, input_files, affines, output_file, weight_file=None, mask_file=None, out_shape=None,
-                    center=None, pixscale=None):
+                    center=None, pixscale=None, maps=None, max_tile_error=0.01):
         """Resamples and combines FITS files.  `affines`: one [a00, a01, a02, a10, a11, a12] per file, or None to
         register through the files' celestial WCS (RA---TAN / DEC--TAN headers, as astrometry.net writes them):
         the output grid is then north-up TAN at `center` = (ra, dec) degrees with `pixscale` arcsec per pixel and
         `out_shape` pixels - SWarp's -CENTER / -PIXEL_SCALE / -IMAGE_SIZE (resample_all.sh:334-338) - or, without
         `center`, the first file's own WCS and shape.
+        `maps`: one distortion.PolyMap per file (reference pixel -> input pixel, what ap_register --model polyN writes) used in place
+        of `affines`, linearised per 16 x 64 output tile on the device (ops.poly_tile_affines; ValueError when that would cost more
+        than `max_tile_error` input pixels).
         Flux scale per file = 1 / EXPOSURE (or EXPTIME), except 1.0 for SUM (resample_all.sh:298, 305-309)."""
         import torch
         input_files = [str(f) for f in input_files]
@@ -157,13 +161,13 @@ class ApResample:
         out_wcs = None
         if use_wcs:
             from .. import wcs as apwcs
-            in_wcs = [apwcs.TanWcs.from_header(h) for h in hdrs]
+            in_wcs = [apwcs.from_header(h) for h in hdrs]
             if center is not None:
                 if pixscale is None or out_shape is None:
                     raise RuntimeError('Error, center needs pixscale and out_shape as well.')
                 out_wcs = apwcs.TanWcs.from_center(float(center[0]), float(center[1]), float(pixscale), out_shape)
             else:
-                out_wcs = in_wcs[0]
+                out_wcs = in_wcs[0].tan()                  # the output grid is pure TAN: a SIP input keeps its distortion to itself
                 out_shape = out_shape or in_shape
             fine_affines = None
             if self.oversampling > 1:
@@ -176,6 +180,20 @@ class ApResample:
             self._logger.info(f'Registered {len(in_wcs)} files through their TAN WCS onto a {out_shape[1]}x{out_shape[0]} grid.')
         else:
             fine_affines = None
+            if maps is not None:
+                from .. import ops
+                maps = list(maps)
+                if len(maps) != len(input_files):
+                    raise RuntimeError(f'Error, {len(maps)} distortion maps given for {len(input_files)} files.')
+                n, shape = self.oversampling, out_shape or in_shape
+                if n > 1:
+                    fine_affines, est = ops.poly_tile_affines(maps, (shape[0] * n, shape[1] * n), tile_scale=n, scale=n,
+                                                              max_tile_error=max_tile_error)
+                    affines = np.zeros((len(maps), 6))
+                else:
+                    affines, est = ops.poly_tile_affines(maps, shape, max_tile_error=max_tile_error)
+                self._logger.info(f'Distortion maps of degree {maps[0].degree}: one transform per 16 x 64 output tile, linearisation '
+                                  f'error at most {est:.2e} input pixels.')
         weights = None
         if self.combine == 'WEIGHTED':
             from .. import ops
@@ -224,6 +242,8 @@ class ApResample:
             for k in ('CD1_1', 'CD1_2', 'CD2_1', 'CD2_2', 'CDELT1', 'CDELT2', 'CROTA1', 'CROTA2', 'PC1_1', 'PC1_2', 'PC2_1', 'PC2_2'):
                 if k in hdr:
                     del hdr[k]
+            for k in [k for k in hdr.keys() if apwcs.is_sip_card(k)]:
+                del hdr[k]
             for k, v in out_wcs.header_cards().items():
                 hdr[k] = v
         hdr['TEXPTIME'] = (texp, '[s] Total exposure of the inputs')

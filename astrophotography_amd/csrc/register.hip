@@ -1,9 +1,10 @@
 // F8: star-list frame registration (include/apgpu.h F8; restated in tests/register_model.py).
 //   triangle_build_kernel  the similarity invariants of every triple among the K brightest stars of each frame
 //   triangle_vote_kernel   reference x frame triangle pairs within eps -> votes for their three vertex pairs
-//   nearest_match_kernel   nearest neighbour under a per-frame affine, both directions
+//   nearest_match_kernel   nearest neighbour under a per-frame map (an affine, or the polynomial of DESIGN 4.3e'), both directions
 // All float64, no contraction (-ffp-contract=off): every expression rounds as the NumPy model's does.
 #include "common.h"
+#include "distortion_core.h"
 
 namespace apgpu {
 namespace {
@@ -129,16 +130,50 @@ __global__ __launch_bounds__(kRegBlock) void triangle_vote_kernel(const double *
 
 constexpr int kNearChunk = 1024;                            // stars of the scanned list per LDS chunk
 
-__device__ __forceinline__ double2 apply_affine(const double *A, double2 r)
-{
-    return make_double2((A[0] * r.x + A[1] * r.y) + A[2], (A[3] * r.x + A[4] * r.y) + A[5]);
-}
+// The map of a frame, reference -> frame, as the kernel's template parameter: the 2x3 affine of apgpu_nearest_match ...
+struct AffineMap {
+    const double *transforms;                               // [F][6]
+    struct Frame {
+        double A[6];
+        __device__ __forceinline__ double2 operator()(double2 r) const
+        {
+            return make_double2((A[0] * r.x + A[1] * r.y) + A[2], (A[3] * r.x + A[4] * r.y) + A[5]);
+        }
+    };
+    __device__ __forceinline__ Frame frame(int f) const
+    {
+        Frame T;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) T.A[i] = transforms[6 * f + i];
+        return T;
+    }
+};
+
+// ... or the polynomial of degree D of apgpu_nearest_match_poly (distortion_core.h); a frame's coefficients are read at a
+// wave-uniform address wherever the map is evaluated.
+template <int D>
+struct PolyMap {
+    const double *coef;                                     // [F][2][ncoef]
+    PolyFrame fr;
+    struct Frame {
+        const double *c;
+        PolyFrame fr;
+        __device__ __forceinline__ double2 operator()(double2 r) const
+        {
+            double X, Y;
+            poly_eval<D>(c, fr, r.x, r.y, X, Y);
+            return make_double2(X, Y);
+        }
+    };
+    __device__ __forceinline__ Frame frame(int f) const { return Frame{coef + (size_t)f * 2 * poly_ncoef(D), fr}; }
+};
 
 // Block (bx, f, dir).  dir 0: query = T_f(reference star), scanned list = the stars of frame f.  dir 1: query = a star of frame
 // f, scanned list = T_f(reference stars).  The scan runs in ascending index and replaces on strictly smaller d2 only: the
 // lexicographic (d2, index) minimum.
-__global__ __launch_bounds__(kRegBlock) void nearest_match_kernel(const double *__restrict__ xy, const int *__restrict__ count,
-                                                                  const double *__restrict__ transforms, int M, double radius2,
+template <class Map>
+__global__ __launch_bounds__(kRegBlock) void nearest_match_kernel(const double *__restrict__ xy, const int *__restrict__ count, const Map map,
+                                                                  int M, double radius2,
                                                                   int *__restrict__ fwd_idx, double *__restrict__ fwd_d2,
                                                                   int *__restrict__ bwd_idx, double *__restrict__ bwd_d2)
 {
@@ -149,9 +184,7 @@ __global__ __launch_bounds__(kRegBlock) void nearest_match_kernel(const double *
     const int nq = dir == 0 ? n0 : nf, ns = dir == 0 ? nf : n0;
     const double2 *ref = reinterpret_cast<const double2 *>(xy);
     const double2 *frm = ref + (size_t)f * M;
-    double A[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) A[i] = transforms[6 * f + i];
+    const typename Map::Frame T = map.frame(f);
     const int q = blockIdx.x * kRegBlock + tid;
     int *out_idx = (dir == 0 ? fwd_idx : bwd_idx) + (size_t)f * M;
     double *out_d2 = (dir == 0 ? fwd_d2 : bwd_d2) + (size_t)f * M;
@@ -159,11 +192,11 @@ __global__ __launch_bounds__(kRegBlock) void nearest_match_kernel(const double *
     double best_d2 = __builtin_inf();
     if ((int)(blockIdx.x * kRegBlock) < nq) {               // (the same for the whole block)
         double2 p = make_double2(0.0, 0.0);
-        if (q < nq) p = dir == 0 ? apply_affine(A, ref[q]) : frm[q];
+        if (q < nq) p = dir == 0 ? T(ref[q]) : frm[q];
         for (int base = 0; base < ns; base += kNearChunk) {
             const int m = min(kNearChunk, ns - base);
             __syncthreads();
-            for (int r = tid; r < m; r += kRegBlock) s[r] = dir == 0 ? frm[base + r] : apply_affine(A, ref[base + r]);
+            for (int r = tid; r < m; r += kRegBlock) s[r] = dir == 0 ? frm[base + r] : T(ref[base + r]);
             __syncthreads();
             if (q < nq) {
 #pragma unroll 4
@@ -185,6 +218,27 @@ __global__ __launch_bounds__(kRegBlock) void nearest_match_kernel(const double *
 }
 
 long long n_triples(int k) { return (long long)k * (k - 1) * (k - 2) / 6; }
+
+int nearest_match_check(const char *what, const double *xy, const int32_t *count, const double *map, int32_t n_frames, int32_t max_stars,
+                        double radius, int32_t *fwd_idx, double *fwd_d2, int32_t *bwd_idx, double *bwd_d2)
+{
+    if (n_frames < 1 || n_frames > 65535) return fail(APGPU_EINVAL, "%s: %d frames (1 .. 65535)", what, n_frames);
+    if (max_stars < 1 || max_stars > kRegMaxStars)
+        return fail(APGPU_EINVAL, "%s: list length %d is outside 1 .. %d", what, max_stars, kRegMaxStars);
+    if (!(radius >= 0.0)) return fail(APGPU_EINVAL, "%s: radius %g is negative or NaN", what, radius);
+    if (!xy || !count || !map || !fwd_idx || !fwd_d2 || !bwd_idx || !bwd_d2) return fail(APGPU_EINVAL, "%s: NULL pointer argument", what);
+    return APGPU_OK;
+}
+
+template <class Map>
+int nearest_match_launch(const char *what, const Map &map, const double *xy, const int32_t *count, int32_t n_frames, int32_t max_stars,
+                         double radius, int32_t *fwd_idx, double *fwd_d2, int32_t *bwd_idx, double *bwd_d2, void *stream)
+{
+    const unsigned blocks = (unsigned)((max_stars + kRegBlock - 1) / kRegBlock);
+    hipLaunchKernelGGL(nearest_match_kernel<Map>, dim3(blocks, (unsigned)n_frames, 2u), dim3(kRegBlock), 0, as_stream(stream), xy, count, map,
+                       (int)max_stars, radius * radius, fwd_idx, fwd_d2, bwd_idx, bwd_d2);
+    return check_launch(what);
+}
 
 }  // namespace
 }  // namespace apgpu
@@ -238,14 +292,31 @@ extern "C" int apgpu_nearest_match(const double *xy, const int32_t *count, const
                                    int32_t max_stars, double radius, int32_t *fwd_idx, double *fwd_d2, int32_t *bwd_idx,
                                    double *bwd_d2, void *stream)
 {
-    if (n_frames < 1 || n_frames > 65535) return fail(APGPU_EINVAL, "nearest_match: %d frames (1 .. 65535)", n_frames);
-    if (max_stars < 1 || max_stars > kRegMaxStars)
-        return fail(APGPU_EINVAL, "nearest_match: list length %d is outside 1 .. %d", max_stars, kRegMaxStars);
-    if (!(radius >= 0.0)) return fail(APGPU_EINVAL, "nearest_match: radius %g is negative or NaN", radius);
-    if (!xy || !count || !transforms || !fwd_idx || !fwd_d2 || !bwd_idx || !bwd_d2)
-        return fail(APGPU_EINVAL, "nearest_match: NULL pointer argument");
-    const unsigned blocks = (unsigned)((max_stars + kRegBlock - 1) / kRegBlock);
-    hipLaunchKernelGGL(nearest_match_kernel, dim3(blocks, (unsigned)n_frames, 2u), dim3(kRegBlock), 0, as_stream(stream), xy, count,
-                       transforms, (int)max_stars, radius * radius, fwd_idx, fwd_d2, bwd_idx, bwd_d2);
-    return check_launch("nearest_match");
+    if (int rc = nearest_match_check("nearest_match", xy, count, transforms, n_frames, max_stars, radius, fwd_idx, fwd_d2, bwd_idx, bwd_d2))
+        return rc;
+    return nearest_match_launch("nearest_match", AffineMap{transforms}, xy, count, n_frames, max_stars, radius, fwd_idx, fwd_d2, bwd_idx,
+                                bwd_d2, stream);
+}
+
+extern "C" int apgpu_nearest_match_poly(const double *xy, const int32_t *count, const double *coef, int32_t degree, double x0, double y0,
+                                        double scale_l, int32_t n_frames, int32_t max_stars, double radius, int32_t *fwd_idx,
+                                        double *fwd_d2, int32_t *bwd_idx, double *bwd_d2, void *stream)
+{
+    const char *what = "nearest_match_poly";
+    if (int rc = nearest_match_check(what, xy, count, coef, n_frames, max_stars, radius, fwd_idx, fwd_d2, bwd_idx, bwd_d2)) return rc;
+    if (degree < 1 || degree > kPolyMaxDegree) return fail(APGPU_EINVAL, "%s: degree %d is outside 1 .. %d", what, degree, kPolyMaxDegree);
+    if (!(is_finite(x0) && is_finite(y0) && is_finite(scale_l) && scale_l > 0.0))
+        return fail(APGPU_EINVAL, "%s: origin (%g, %g) must be finite and L = %g finite and positive", what, x0, y0, scale_l);
+    const PolyFrame fr{x0, y0, scale_l};
+#define APGPU_NEAREST_POLY(D) \
+    case D: return nearest_match_launch(what, PolyMap<D>{coef, fr}, xy, count, n_frames, max_stars, radius, fwd_idx, fwd_d2, bwd_idx, bwd_d2, stream)
+    switch (degree) {
+        APGPU_NEAREST_POLY(1);
+        APGPU_NEAREST_POLY(2);
+        APGPU_NEAREST_POLY(3);
+        APGPU_NEAREST_POLY(4);
+    default:
+        APGPU_NEAREST_POLY(5);
+    }
+#undef APGPU_NEAREST_POLY
 }

@@ -2133,20 +2133,42 @@ def triangle_vote(tri, eps=0.002, allow_mirror=False):
     return votes
 
 
-def nearest_match(xy, count, transforms, radius):
-    """Nearest neighbours under per-frame affines (transforms [F, 6], reference -> frame): fwd_idx / fwd_d2 [F, M] for every
-    reference star the nearest star of frame f to its image and the squared distance, bwd_idx / bwd_d2 [F, M] for every star of
-    frame f the reference star whose image is nearest.  Only neighbours with d2 <= radius^2 (inclusive) count; ties go to the
-    lower index; no neighbour: -1 and inf.  Device tensors."""
+def _poly_maps(maps, n, what='maps'):
+    """maps: a sequence of n distortion.PolyMap of one degree, origin and scale, or (coef [n, 2, ncoef], (x0, y0), L).
+    -> (coef float64 numpy [n, 2, ncoef], degree, x0, y0, L), checked."""
+    from . import distortion
+    if isinstance(maps, tuple) and len(maps) == 3 and not isinstance(maps[0], distortion.PolyMap):
+        coef = np.array(maps[0], dtype=np.float64)
+        if coef.ndim != 3 or coef.shape[1] != 2:
+            raise ValueError('%s: the coefficients must be [frames, 2, ncoef], got %s' % (what, coef.shape))
+        maps = [distortion.PolyMap(c[0], c[1], maps[1], maps[2]) for c in coef]
+    maps = list(maps)
+    if len(maps) != n or not all(isinstance(m, distortion.PolyMap) for m in maps):
+        raise ValueError('%s must hold one PolyMap per frame (%d)' % (what, n))
+    return distortion.stack_coefficients(maps)
+
+
+def nearest_match(xy, count, transforms, radius, maps=None):
+    """Nearest neighbours under per-frame maps, reference -> frame: affines (transforms [F, 6]) or, with maps= (one
+    distortion.PolyMap per frame, one degree, origin and scale; transforms is then not looked at), polynomials.  fwd_idx / fwd_d2
+    [F, M] for every reference star the nearest star of frame f to its image and the squared distance, bwd_idx / bwd_d2 [F, M] for
+    every star of frame f the reference star whose image is nearest.  Only neighbours with d2 <= radius^2 (inclusive) count; ties
+    go to the lower index; no neighbour: -1 and inf.  Device tensors."""
     xy, count = _star_lists(xy, count)
     F, M = int(xy.shape[0]), int(xy.shape[1])
     if M > _lib.REGISTER_MAX_STARS:
         raise ValueError('lists of %d stars: at most %d' % (M, _lib.REGISTER_MAX_STARS))
-    T = torch.as_tensor(np.asarray(transforms, np.float64).reshape(F, 6)).to(xy.device).contiguous()
     idx = torch.empty((2, F, M), dtype=torch.int32, device=xy.device)
     d2 = torch.empty((2, F, M), dtype=torch.float64, device=xy.device)
-    check(_lib.load().apgpu_nearest_match(_ptr(xy), _ptr(count), _ptr(T), F, M, float(radius), _ptr(idx[0]), _ptr(d2[0]), _ptr(idx[1]),
-                                          _ptr(d2[1]), _stream()))
+    if maps is None:
+        T = torch.as_tensor(np.asarray(transforms, np.float64).reshape(F, 6)).to(xy.device).contiguous()
+        check(_lib.load().apgpu_nearest_match(_ptr(xy), _ptr(count), _ptr(T), F, M, float(radius), _ptr(idx[0]), _ptr(d2[0]), _ptr(idx[1]),
+                                              _ptr(d2[1]), _stream()))
+    else:
+        coef, degree, x0, y0, L = _poly_maps(maps, F)
+        T = torch.from_numpy(np.ascontiguousarray(coef)).to(xy.device)
+        check(_lib.load().apgpu_nearest_match_poly(_ptr(xy), _ptr(count), _ptr(T), degree, x0, y0, L, F, M, float(radius), _ptr(idx[0]),
+                                                   _ptr(d2[0]), _ptr(idx[1]), _ptr(d2[1]), _stream()))
     return dict(fwd_idx=idx[0], fwd_d2=d2[0], bwd_idx=idx[1], bwd_d2=d2[1])
 
 
@@ -2184,6 +2206,62 @@ def _register_seeds(V):
     return np.stack([i[ok], row_best[ok]], axis=1).astype(np.int64)
 
 
+REGISTER_POLY_MODELS = ('poly2', 'poly3', 'poly4', 'poly5')
+
+
+def _register_polynomial(out, xy, count, degree, match_radius, max_rounds):
+    """Step 7 of DESIGN 4.3e': `out` is register_lists' result with the affine model; adds the polynomial of `degree`."""
+    from .distortion import PolyMap, ncoef
+    xy, count = _star_lists(xy, count)
+    F, M = int(xy.shape[0]), int(xy.shape[1])
+    pts, cnt = xy.cpu().numpy(), np.clip(count.cpu().numpy(), 0, M)
+    ref = pts[0, :cnt[0]]
+    if cnt[0] > 0:
+        lo, hi = ref.min(axis=0), ref.max(axis=0)
+        origin, L = (float(0.5 * (lo[0] + hi[0])), float(0.5 * (lo[1] + hi[1]))), float(0.5 * np.hypot(hi[0] - lo[0], hi[1] - lo[1]))
+    else:
+        origin, L = (0.0, 0.0), 1.0
+    L = L if L > 0.0 else 1.0
+    ident = PolyMap.from_affine(REGISTER_IDENTITY, degree, origin, L)
+    maps = [PolyMap.from_affine(out['coeffs'][f], degree, origin, L) if out['ok'][f] else ident for f in range(F)]
+    out.update(order=np.ones(F, np.int64), origin=origin, scale=L, rms_affine=out['rms'].copy())
+    rms, pairs = out['rms'].copy(), [None] * F
+    live = [f for f in range(1, F) if out['ok'][f]]
+    fitted = {}
+    for rnd in range(max_rounds):
+        if not live:
+            break
+        radius = {f: float(np.clip(3.0 * rms[f], 0.5, match_radius)) for f in live}
+        found = {}
+        for rad in sorted(set(radius.values())):
+            nm = nearest_match(xy, count, None, rad, maps=maps)
+            fwd, bwd = nm['fwd_idx'].cpu().numpy(), nm['bwd_idx'].cpu().numpy()
+            for f in live:
+                if radius[f] == rad:
+                    i = np.nonzero(fwd[f] >= 0)[0]
+                    i = i[bwd[f][fwd[f][i]] == i]
+                    found[f] = np.stack([i, fwd[f][i]], axis=1).astype(np.int64)
+        still = []
+        for f in live:
+            if pairs[f] is not None and np.array_equal(found[f], pairs[f]):
+                continue
+            pairs[f] = found[f]
+            m = None
+            if len(pairs[f]) >= 3 * ncoef(degree):
+                m, _, r = PolyMap.fit(pts[0, pairs[f][:, 0]], pts[f, pairs[f][:, 1]], degree, origin, L)
+            if m is None:                                    # too few pairs or a rank-deficient design: the frame keeps its affine
+                fitted.pop(f, None)
+                maps[f] = PolyMap.from_affine(out['coeffs'][f], degree, origin, L)
+                continue
+            maps[f], rms[f], fitted[f] = m, r, pairs[f]
+            still.append(f)
+        live = still
+    for f, pr in fitted.items():
+        out['order'][f], out['rms'][f], out['n_matched'][f], out['pairs'][f] = degree, rms[f], len(pr), pr
+    out['maps'] = [maps[f] if out['ok'][f] else None for f in range(F)]
+    return out
+
+
 def register_lists(xy, count, K=40, eps=0.002, min_side=5.0, match_radius=3.0, model='affine', allow_mirror=False, max_rounds=4):
     """Registers frames 1 .. F-1 on frame 0 from their star lists (xy [F, M, 2] float64, x = column, 0-based pixel centres,
     brightest first, padded; count [F]): triangle votes among the K brightest stars -> seed pairs -> a similarity fit -> up to
@@ -2194,9 +2272,19 @@ def register_lists(xy, count, K=40, eps=0.002, min_side=5.0, match_radius=3.0, m
     Returns a dict over frames: coeffs [F, 6] (x_frame = a0 x + a1 y + a2, y_frame = a3 x + a4 y + a5 for x, y on the grid of
     frame 0: what resample_affine and ap_coadd take; NaN where not ok), ok [F] bool, n_seed, n_matched [F], rms [F] (the 2-D
     rms of the matched pairs about the fit, pixels), pairs (per frame [n, 2]: reference index, frame index) and votes (device).
-    A frame that cannot be registered has ok = False: that is a status, not an error.  Frame 0 gets the identity."""
-    if model not in ('affine', 'similarity'):
-        raise ValueError("model must be 'affine' or 'similarity', got %r" % (model,))
+    A frame that cannot be registered has ok = False: that is a status, not an error.  Frame 0 gets the identity.
+
+    model 'poly2' .. 'poly5' (DESIGN 4.3e'): the steps above with the affine model, then for every ok frame a polynomial of that
+    degree (distortion.PolyMap), refined from the affine by up to max_rounds rounds of (mutual nearest neighbours under the
+    polynomial at clip(3 rms, 0.5, match_radius), refit) until the pair set repeats.  The result then also holds maps (a PolyMap
+    per frame, None where not ok), order [F] (the degree; 1 where the frame keeps its affine - fewer than 3 ncoef pairs or a
+    rank-deficient design, a status too - and for frame 0), origin (the midpoint of the bounding box of frame 0's stars), scale
+    (half its diagonal) and rms_affine; rms, n_matched and pairs are the polynomial's where order > 1; coeffs stays the affine."""
+    if model not in ('affine', 'similarity') + REGISTER_POLY_MODELS:
+        raise ValueError("model must be 'affine', 'similarity' or 'poly2' .. 'poly5', got %r" % (model,))
+    if model in REGISTER_POLY_MODELS:
+        out = register_lists(xy, count, K, eps, min_side, match_radius, 'affine', allow_mirror, max_rounds)
+        return _register_polynomial(out, xy, count, int(model[4:]), match_radius, max_rounds)
     xy, count = _star_lists(xy, count)
     F, M = int(xy.shape[0]), int(xy.shape[1])
     tri = triangle_build(xy, count, K, min_side)
@@ -3001,8 +3089,27 @@ def _drizzle_frames(frames):
     return frames
 
 
-def _drizzle_affines(affines, N):
-    a = np.array(torch.as_tensor(affines, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(-1, 6)
+def _drizzle_tile_shape(shape):
+    """The grid of 16 x 64 pixel tiles over an image: the per-tile transforms of drizzle (output tiles) and drizzle_reject (input)."""
+    return -(-int(shape[0]) // 16), -(-int(shape[1]) // 64)
+
+
+def _drizzle_affines(affines, N, tile_shape=None):
+    """float64 numpy [N, 6]: one transform per frame - or, when `affines` is [N, ty, tx, 6], [N ty tx, 6]: one per frame and tile of
+    the grid `tile_shape` (checked).  -> (transforms, per_tile)."""
+    a = np.array(torch.as_tensor(affines, dtype=torch.float64).cpu().numpy(), dtype=np.float64)
+    if a.ndim == 4:
+        if tile_shape is None or tuple(a.shape) != (N,) + tuple(tile_shape) + (6,):
+            raise ValueError('per-tile transforms must be [N, %s, %s, 6] (tiles of 16 x 64 pixels), got %s'
+                             % (tile_shape[0] if tile_shape else '?', tile_shape[1] if tile_shape else '?', a.shape))
+        if not np.all(np.isfinite(a)):
+            raise ValueError('the transforms must be finite')
+        return a.reshape(-1, 6), True
+    return _drizzle_frame_affines(a, N), False
+
+
+def _drizzle_frame_affines(a, N):
+    a = a.reshape(-1, 6)
     if a.shape[0] == 1 and N > 1:
         a = np.repeat(a, N, 0)
     if a.shape[0] != N:
@@ -3056,7 +3163,8 @@ def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, 
     `scale` output pixels per reference pixel, in one launch (include/apgpu.h F14).
 
     affines: one 2x3 float64 transform per frame, reference pixel -> input pixel, as resample_affine takes them (ap_register writes
-    them).  pixfrac: the side of a drop in input pixels, (0, 1].  fscale: per-frame flux scale; conserve_flux also multiplies by
+    them); or [N, ty, tx, 6], one per frame and 16 x 64 tile of the OUTPUT, reference pixel -> input pixel about that tile
+    (poly_tile_affines(..., composed=False): a lens distortion): footprint, weight and flux factor are then the tile's own.  pixfrac: the side of a drop in input pixels, (0, 1].  fscale: per-frame flux scale; conserve_flux also multiplies by
     |det| of the composed transform (surface brightness otherwise).  weights: one finite, positive weight per frame (None: 1).
     mask [H,W] / frame_masks [N,H,W]: non-zero = bad pixel.  out_shape: (h, w) of the output, default drizzle_out_shape.  cfa:
     (pattern, channel) - only pixels of that colour feed the plane: pattern as bayer_pattern gives it, channel 0 (R), 1 (G, both
@@ -3070,20 +3178,27 @@ def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, 
     p = np.float32(pixfrac)
     if not (p > 0 and p <= 1):
         raise ValueError('pixfrac must be in (0, 1], got %r' % (pixfrac,))
-    A = drizzle_affines(_drizzle_affines(affines, N), scale)
+    h, wo = drizzle_out_shape((H, W), scale) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
+    if h < 1 or wo < 1:
+        raise ValueError('out_shape must be positive, got %r' % (out_shape,))
+    A, per_tile = _drizzle_affines(affines, N, _drizzle_tile_shape((h, wo)))
+    A = drizzle_affines(A, scale)
     if not np.all(np.isfinite(A)):
         raise ValueError('the transforms must be finite')
     hx, hy = 0.5 * np.hypot(A[:, 0], A[:, 3]), 0.5 * np.hypot(A[:, 1], A[:, 4])
     lx, ly = 2.0 * hx, 2.0 * hy
     if not (np.all(lx > 0.0) and np.all(lx <= 2.0) and np.all(ly > 0.0) and np.all(ly <= 2.0)):
         raise ValueError('the footprint of an output pixel must be within (0, 2] input pixels per axis, got %s x %s: '
-                         'use a larger scale' % (lx.tolist(), ly.tolist()))
+                         'use a larger scale' % ((lx.tolist(), ly.tolist()) if not per_tile else
+                                                 ('%g .. %g' % (lx.min(), lx.max()), '%g .. %g over the tiles' % (ly.min(), ly.max()))))
     fs = _drizzle_f32n(fscale, N, 'fscale', 1.0)
     w = _drizzle_f32n(weights, N, 'weights', 1.0)
     if not np.all(np.isfinite(fs)):
         raise ValueError('fscale must be finite')
     if not (np.all(np.isfinite(w)) and np.all(w > 0)):
         raise ValueError('weights must be finite and positive')
+    if per_tile:                                                         # a frame's values, once per tile of the frame
+        fs, w = np.repeat(fs, A.shape[0] // N), np.repeat(w, A.shape[0] // N)
     g = fs
     if conserve_flux:
         g = (fs.astype(np.float64) * np.abs(A[:, 0] * A[:, 4] - A[:, 1] * A[:, 3])).astype(np.float32)
@@ -3097,15 +3212,13 @@ def drizzle(frames, affines, scale=2.0, pixfrac=0.5, fscale=None, weights=None, 
         pat = (C.c_int32 * 4)(*bayer_pattern(pattern))
         if isinstance(channel, bool) or int(channel) != channel or int(channel) not in (0, 1, 2):
             raise ValueError('the cfa channel must be 0 (R), 1 (G) or 2 (B), got %r' % (channel,))
-    h, wo = drizzle_out_shape((H, W), scale) if out_shape is None else (int(out_shape[0]), int(out_shape[1]))
-    if h < 1 or wo < 1:
-        raise ValueError('out_shape must be positive, got %r' % (out_shape,))
     prm = np.concatenate([A, hx[:, None], hy[:, None], w.astype(np.float64)[:, None], g.astype(np.float64)[:, None]], 1)
     prm = torch.from_numpy(np.ascontiguousarray(prm)).to(dev)
     image = torch.empty((h, wo), dtype=torch.float32, device=dev)
     weight = torch.empty((h, wo), dtype=torch.float32, device=dev)
-    check(_lib.load().apgpu_drizzle_f32(_ptr(frames), N, H, W, _ptr(mk), _ptr(fm), _ptr(prm), float(p), pat, int(channel), _ptr(image),
-                                        _ptr(weight), h, wo, _stream()))
+    lib = _lib.load()
+    entry = lib.apgpu_drizzle_tiles_f32 if per_tile else lib.apgpu_drizzle_f32
+    check(entry(_ptr(frames), N, H, W, _ptr(mk), _ptr(fm), _ptr(prm), float(p), pat, int(channel), _ptr(image), _ptr(weight), h, wo, _stream()))
     return dict(image=image, weight=weight)
 
 
@@ -3115,7 +3228,9 @@ def drizzle_reject(frames, affines, ref, ref_scale=1.0, fscale=None, sigmas=None
     pixels b comes from (it keeps undersampled star cores from being flagged).  ref: float32 [hr, wr] on the grid with `ref_scale`
     pixels per reference pixel (a median co-add at 1, a first drizzle at its scale), in flux-scaled units.  sigmas: per-frame noise in
     those units (fscale_i times the frame's clipped standard deviation).  Pixels under which the reference is missing or not finite are not
-    flagged.  Returns uint8 [N, H, W], 1 = outlier: drizzle's frame_masks."""
+    flagged.  affines: as drizzle's, or [N, ty, tx, 6], one per frame and 16 x 64 tile of the INPUT frame, reference pixel -> input
+    pixel about the point that maps to that tile (poly_input_tile_affines).  Returns uint8 [N, H, W], 1 = outlier: drizzle's
+    frame_masks."""
     import math
     frames = _drizzle_frames(frames)
     N, H, W = frames.shape
@@ -3130,7 +3245,7 @@ def drizzle_reject(frames, affines, ref, ref_scale=1.0, fscale=None, sigmas=None
     kf, gf = np.float32(k), np.float32(grow)
     if not (np.isfinite(kf) and np.isfinite(gf) and kf >= 0 and gf >= 0):
         raise ValueError('k and grow must be finite and >= 0, got %r and %r' % (k, grow))
-    a = _drizzle_affines(affines, N)
+    a, per_tile = _drizzle_affines(affines, N, _drizzle_tile_shape((H, W)))
     det = a[:, 0] * a[:, 4] - a[:, 1] * a[:, 3]
     if not np.all(np.isfinite(det)) or np.any(det == 0.0):
         raise ValueError('a transform is singular')
@@ -3146,9 +3261,66 @@ def drizzle_reject(frames, affines, ref, ref_scale=1.0, fscale=None, sigmas=None
     sg = _drizzle_f32n(sigmas, N, 'sigmas', 0.0)
     if not (np.all(np.isfinite(fs)) and np.all(np.isfinite(sg)) and np.all(sg >= 0)):
         raise ValueError('fscale must be finite and sigmas finite and >= 0')
+    if per_tile:
+        fs, sg = np.repeat(fs, a.shape[0] // N), np.repeat(sg, a.shape[0] // N)
     prm = np.concatenate([B, fs.astype(np.float64)[:, None], sg.astype(np.float64)[:, None]], 1)
     prm = torch.from_numpy(np.ascontiguousarray(prm)).to(dev)
     out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
-    check(_lib.load().apgpu_drizzle_reject_u8(_ptr(frames), N, H, W, _ptr(prm), _ptr(ref), ref.shape[0], ref.shape[1], float(kf), float(gf),
-                                              _ptr(out), _stream()))
+    lib = _lib.load()
+    entry = lib.apgpu_drizzle_reject_tiles_u8 if per_tile else lib.apgpu_drizzle_reject_u8
+    check(entry(_ptr(frames), N, H, W, _ptr(prm), _ptr(ref), ref.shape[0], ref.shape[1], float(kf), float(gf), _ptr(out), _stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F19: lens distortion - polynomial maps (distortion.py) as the per-tile transforms the resample and drizzle kernels take
+# (csrc/distortion.hip, DESIGN 4.3e')
+def poly_tile_affines(maps, out_shape, tile_scale=1, scale=1.0, max_tile_error=0.01, composed=True, device='cuda'):
+    """The linearisation of per-frame distortion maps (distortion.PolyMap, reference pixel -> input pixel; one degree, origin and
+    scale) over the tiles of 16 tile_scale x 64 tile_scale pixels of an out_shape grid with `scale` pixels per reference pixel (grid
+    pixel (u, v) at reference coordinate ((u + 0.5) / scale - 0.5, (v + 0.5) / scale - 0.5)): the map and its analytic Jacobian at
+    the tile centre, written on the device.  scale 1: the co-add's grid, for resample_affine / coadd; OVERSAMPLING n: scale = n,
+    tile_scale = n, for resample_oversampled(fine_affines=).  composed=False: transforms of REFERENCE pixels instead of grid pixels,
+    what drizzle takes (it composes with its grid itself).
+
+    Returns (float64 device tensor [N, tiles_y, tiles_x, 6], the largest PolyMap.tile_error estimate in input pixels); ValueError
+    when the estimate exceeds max_tile_error."""
+    import math
+    maps = list(maps) if not isinstance(maps, tuple) else maps
+    h, w = int(out_shape[0]), int(out_shape[1])
+    ts, s = int(tile_scale), float(scale)
+    if h < 1 or w < 1:
+        raise ValueError('out_shape must be positive, got %r' % (out_shape,))
+    if ts != tile_scale or not 1 <= ts <= 16:
+        raise ValueError('tile_scale must be 1 .. 16, got %r' % (tile_scale,))
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError('scale must be a positive number, got %r' % (scale,))
+    coef, degree, x0, y0, L = _poly_maps(maps, len(maps[0]) if isinstance(maps, tuple) else len(maps))
+    from .distortion import PolyMap
+    est = max(PolyMap(c[0], c[1], (x0, y0), L).tile_error((h, w), ts, s) for c in coef)
+    if not est <= float(max_tile_error):
+        raise ValueError('the tiles of %d x %d pixels linearise this map to %.3g input pixels, more than max_tile_error = %g'
+                         % (64 * ts, 16 * ts, est, max_tile_error))
+    N = coef.shape[0]
+    ty, tx = -(-h // (16 * ts)), -(-w // (64 * ts))
+    dev = torch.device(device)
+    c = torch.from_numpy(np.ascontiguousarray(coef)).to(dev)
+    out = torch.empty((N, ty, tx, 6), dtype=torch.float64, device=c.device)
+    check(_lib.load().apgpu_poly_tile_affines(_ptr(c), N, degree, x0, y0, L, h, w, ts, s, int(bool(composed)), _ptr(out), _stream()))
+    return out, est
+
+
+def poly_input_tile_affines(maps, in_shape):
+    """For drizzle_reject under distortion maps: float64 numpy [N, ty, tx, 6], per frame and 16 x 64 tile of the INPUT frame the
+    transform reference pixel -> input pixel about the reference point p that maps to the tile centre c (PolyMap.inverse, host):
+    the Jacobian at p, and the offset that takes p to c.  NaN where the inverse does not converge (drizzle_reject refuses it)."""
+    maps = list(maps)
+    ty, tx = _drizzle_tile_shape(in_shape)
+    yc = np.arange(ty, dtype=np.float64)[:, None] * 16.0 + 7.5 + np.zeros((1, tx))
+    xc = np.arange(tx, dtype=np.float64)[None, :] * 64.0 + 31.5 + np.zeros((ty, 1))
+    out = np.empty((len(maps), ty, tx, 6))
+    for m, o in zip(maps, out):
+        px, py = m.inverse(xc, yc)
+        a0, a1, a3, a4 = m.jacobian(px, py)
+        o[...] = np.stack([a0, a1, (xc - a0 * px) - a1 * py, a3, a4, (yc - a3 * px) - a4 * py], axis=-1)
     return out

@@ -5,6 +5,10 @@ reference's scripts/resample_all.sh:330-342).  Transforms come from a YAML file:
     transforms:
       frame-0001.fits: [1.0, 0.0, 0.0, 0.0, 1.0, 0.0]     # xin = a0*x + a1*y + a2 ; yin = a3*x + a4*y + a5
       frame-0002.fits: [0.99999, -0.0035, 1.25, 0.0035, 0.99999, -0.75]
+
+A file written by ``ap_register --model poly3`` also holds ``distortion:`` (a polynomial map per frame, DESIGN 4.3e'), which is used
+in place of the affines unless --ignore_distortion is given.  Without --transforms the frames are registered through their headers:
+RA---TAN / DEC--TAN, with or without SIP distortion terms.
 """
 import argparse
 import logging
@@ -51,8 +55,25 @@ def command_line_opts(argv):
                         help='WINSORIZED, MINMAX and ESD: normalise LOCALLY - the statistics are taken per box of PIXELS x PIXELS and scale and '
                              'offset are interpolated at every pixel, for frames whose sky differs in shape (moon, light dome, '
                              'meridian flip). Default: one scale and one offset per frame')
+    parser.add_argument('--ignore_distortion', default=False, action='store_true',
+                        help='Use the affines of the transforms file even when it holds a distortion entry (ap_register --model polyN).')
+    parser.add_argument('--max_tile_error', default=0.01, type=float, metavar='PIXELS',
+                        help='Distortion: refuse maps whose linearisation per 16 x 64 tile costs more than this. Default: 0.01')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
     return parser.parse_args(argv)
+
+
+def distortion_maps(doc, input_images, ignore=False):
+    """The distortion maps of the input files from a transforms document (its `distortion:` entry, as ap_register --model polyN
+    writes it), or None when it has none or `ignore` is set."""
+    entry = doc.get('distortion')
+    if entry is None or ignore:
+        return None
+    from astrophotography_amd.distortion import from_document
+    try:
+        return from_document(entry, input_images)
+    except ValueError as err:
+        raise RuntimeError(f'Error, {err}.') from err
 
 
 def main(args=None):
@@ -61,11 +82,13 @@ def main(args=None):
     from astrophotography_amd.core.ApResample import ApResample
     affines = None
     table = None
+    maps = None
     if p.transforms is not None:
         with open(p.transforms) as fh:
             doc = yaml.safe_load(fh) or {}
         table = doc.get('transforms') or {}
         affines = []
+        maps = distortion_maps(doc, p.input_images, p.ignore_distortion)
     for f in (p.input_images if table is not None else []):
         key = f if f in table else os.path.basename(f)
         if key not in table:
@@ -85,7 +108,7 @@ def main(args=None):
     if p.center:
         center = tuple(float(v) for v in p.center.split(','))
     rs.coadd_files(p.input_images, affines, p.output_image, weight_file=p.weight_image, mask_file=p.badpix, out_shape=out_shape,
-                   center=center, pixscale=p.pixelscale)
+                   center=center, pixscale=p.pixelscale, maps=maps, max_tile_error=p.max_tile_error)
     return 0
 
 

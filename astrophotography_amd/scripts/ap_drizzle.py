@@ -33,6 +33,10 @@ def command_line_opts(argv):
     parser.add_argument('--image_size', default=None, metavar='NX,NY', help='Output size (default: the input size times the scale).')
     parser.add_argument('--no_weighting', default=False, action='store_true', help='Equal frame weights instead of inverse background variance.')
     parser.add_argument('--conserve_flux', default=False, action='store_true', help='Keep totals (scale by the pixel-area ratio) instead of surface brightness.')
+    parser.add_argument('--ignore_distortion', default=False, action='store_true',
+                        help='Use the affines of the transforms file even when it holds a distortion entry (ap_register --model polyN).')
+    parser.add_argument('--max_tile_error', default=0.01, type=float, metavar='PIXELS',
+                        help='Distortion: refuse maps whose linearisation per 16 x 64 tile costs more than this. Default: 0.01')
     parser.add_argument('-l', '--loglevel', default='INFO', help='Logging message level. Default: INFO')
     return parser.parse_args(argv)
 
@@ -58,8 +62,9 @@ def main(args=None):
         out_shape = (ny, nx)
     dz = ApDrizzle(p.loglevel, scale=p.scale, pixfrac=p.pixfrac, reject=p.reject, k=p.k, grow=p.grow,
                    weighting='none' if p.no_weighting else 'background', conserve_flux=p.conserve_flux)
+    from astrophotography_amd.scripts.ap_coadd import distortion_maps
     dz.drizzle_files(p.input_images, affines, p.output_image, weight_file=p.weight_image, mask_file=p.badpix, cfa=p.cfa, pattern=p.pattern,
-                     out_shape=out_shape)
+                     out_shape=out_shape, maps=distortion_maps(doc, p.input_images, p.ignore_distortion), max_tile_error=p.max_tile_error)
     return 0
 
 

@@ -20,7 +20,9 @@ def command_line_opts(argv):
                         help='Triangles are built from the K brightest stars of each list (3 .. 64). Default: 40')
     parser.add_argument('--eps', default=0.002, type=float, help='Tolerance on the triangle invariants. Default: 0.002')
     parser.add_argument('--match_radius', default=3.0, type=float, metavar='PIXELS', help='Largest match distance. Default: 3.0')
-    parser.add_argument('--model', default='affine', choices=['affine', 'similarity'], help='Fitted transform. Default: affine')
+    parser.add_argument('--model', default='affine', choices=['affine', 'similarity', 'poly2', 'poly3', 'poly4', 'poly5'],
+                        help='Fitted transform; polyN adds a distortion polynomial of total degree N to the affine (lens distortion: the '
+                             'file gets a distortion entry that ap_coadd and ap_drizzle use). Default: affine')
     parser.add_argument('--allow_mirror', action='store_true', help='Also match a mirrored frame.')
     parser.add_argument('--skip_failed', action='store_true',
                         help='Leave frames that cannot be registered out of the output, with a warning. Default: an error.')

@@ -36,7 +36,9 @@ extern "C" {
                                        apgpu_gauss2d_fit_f32; apgpu_triangle_build, apgpu_triangle_vote, apgpu_nearest_match;
                                        apgpu_quantile_levels_f32(_ws_bytes), apgpu_composite_rgb;
                                        apgpu_bayer_demosaic, apgpu_bayer_channel_sums;
-                                       apgpu_drizzle_f32, apgpu_drizzle_reject_u8 */
+                                       apgpu_drizzle_f32, apgpu_drizzle_reject_u8;
+                                       apgpu_nearest_match_poly, apgpu_poly_tile_affines, apgpu_drizzle_tiles_f32,
+                                       apgpu_drizzle_reject_tiles_u8 */
 
 /* error codes */
 #define APGPU_OK            0
@@ -1043,6 +1045,49 @@ int apgpu_drizzle_f32(const float *frames, int32_t n_frames, int64_t height, int
                       int64_t out_height, int64_t out_width, void *stream);
 int apgpu_drizzle_reject_u8(const float *frames, int32_t n_frames, int64_t height, int64_t width, const double *params, const float *ref,
                             int64_t ref_height, int64_t ref_width, float k, float grow, uint8_t *mask_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F19 Lens distortion: a polynomial map reference pixel -> input pixel per frame, carried through registration, co-add and drizzle
+ *     (DESIGN 4.3e'; this project's own definition, written once in csrc/distortion_core.h, on the host in
+ *     astrophotography_amd/distortion.py, restated in tests/distortion_model.py).  All float64, every operation rounds on its own.
+ *
+ *     The map: X = Px(u, v), Y = Py(u, v) with u = (x - x0) / L, v = (y - y0) / L, total degree d in 1 .. APGPU_POLY_MAX_DEGREE.
+ *       coef [n_frames][2][ncoef] (x axis, then y axis), ncoef = (d + 1)(d + 2) / 2: coefficient k belongs to u^i v^j, the monomials
+ *       running by total degree t = 0 .. d and within t by j = 0 .. t, i = t - j.  One d, x0, y0 and L per call.
+ *       Powers by repeated multiplication, up[0] = 1, up[i] = up[i-1] u; the sum from +0 in coefficient order, s = s + c[k] (up[i]
+ *       vp[j]).  dX/du likewise from (i c[k]) (up[i-1] vp[j]) over the terms with i >= 1, dX/dv from (j c[k]) (up[i] vp[j-1]) over j >=
+ *       1; a derivative with respect to a pixel coordinate is that sum divided by L.
+ *
+ *     apgpu_nearest_match_poly: apgpu_nearest_match (F8) with T_f the map of frame f in place of the affine; everything else - both
+ *       directions, the tie rule, the inclusive radius, the outputs - as there.
+ *     apgpu_poly_tile_affines: affines [n_frames][tiles_y][tiles_x][6], tiles of 16 tile_scale rows x 64 tile_scale columns of an
+ *       out_height x out_width grid with `scale` = s pixels per reference pixel (tile_scale 1 .. 16): what apgpu_resample_affine_f32
+ *       (per_tile), apgpu_resample_oversampled_f32 and ops.drizzle take.  Tile (ty, tx) has its centre at xc = 64 tile_scale tx + (64
+ *       tile_scale - 1) / 2, yc = 16 tile_scale ty + (16 tile_scale - 1) / 2, at reference coordinates xr = (xc + 0.5) / s - 0.5, yr
+ *       likewise.  With (X, Y) and the derivatives at (xr, yr): a0 = (dX/dx) / s, a1 = (dX/dy) / s, a2 = (X - a0 xc) - a1 yc; a3 =
+ *       (dY/dx) / s, a4 = (dY/dy) / s, a5 = (Y - a3 xc) - a4 yc: an affine of OUTPUT pixels (composed != 0).  composed == 0: an
+ *       affine of REFERENCE pixels about the same point, a0 = dX/dx, a1 = dX/dy, a2 = (X - a0 xr) - a1 yr and a3 .. a5 likewise (what
+ *       ops.drizzle takes and composes with its grid itself).
+ *     apgpu_drizzle_tiles_f32: apgpu_drizzle_f32 (F14) with params [n_frames][tiles_y][tiles_x][10], one record per 16 x 64 OUTPUT
+ *       pixels, tiles_y = ceil(out_height / 16), tiles_x = ceil(out_width / 64); output pixel (u, v) uses record (v / 16, u / 64).
+ *       hx, hy, w and g are the tile's own.
+ *     apgpu_drizzle_reject_tiles_u8: apgpu_drizzle_reject_u8 with params [n_frames][tiles_y][tiles_x][8], one record per 16 x 64
+ *       INPUT pixels, tiles_y = ceil(height / 16), tiles_x = ceil(width / 64); pixel (c, r) uses record (r / 16, c / 64).
+ *     APGPU_EINVAL: as the per-frame entry points, and a degree outside 1 .. 5, an origin or L that is not finite, L <= 0, scale <= 0,
+ *       tile_scale outside 1 .. 16.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_POLY_MAX_DEGREE 5
+int apgpu_nearest_match_poly(const double *xy, const int32_t *count, const double *coef, int32_t degree, double x0, double y0,
+                             double scale_l, int32_t n_frames, int32_t max_stars, double radius, int32_t *fwd_idx, double *fwd_d2,
+                             int32_t *bwd_idx, double *bwd_d2, void *stream);
+int apgpu_poly_tile_affines(const double *coef, int32_t n_frames, int32_t degree, double x0, double y0, double scale_l, int64_t out_height,
+                            int64_t out_width, int32_t tile_scale, double scale, int32_t composed, double *affines, void *stream);
+int apgpu_drizzle_tiles_f32(const float *frames, int32_t n_frames, int64_t height, int64_t width, const uint8_t *mask,
+                            const uint8_t *frame_masks, const double *params, float pixfrac, const int32_t *pattern_host, int32_t channel,
+                            float *image, float *weight, int64_t out_height, int64_t out_width, void *stream);
+int apgpu_drizzle_reject_tiles_u8(const float *frames, int32_t n_frames, int64_t height, int64_t width, const double *params,
+                                  const float *ref, int64_t ref_height, int64_t ref_width, float k, float grow, uint8_t *mask_out,
+                                  void *stream);
 
 #ifdef __cplusplus
 }
