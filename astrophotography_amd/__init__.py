@@ -30,6 +30,7 @@ _LAZY = {
     'ApDeconvolve': ('.core.ApDeconvolve', 'ApDeconvolve'),
     'ApMultiscale': ('.core.ApMultiscale', 'ApMultiscale'),
     'ApDrizzle': ('.core.ApDrizzle', 'ApDrizzle'),
+    'ApRemoveGradient': ('.core.ApRemoveGradient', 'ApRemoveGradient'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -32,6 +32,8 @@ LATE_UNITS = ['stack_reject']
 ESD_UNITS = [('stack_esd_' + tag, 'stack_esd', ['-DAPGPU_ESD_RAW=' + raw, '-DAPGPU_ESD_ENTRY=launch_esd_' + tag]) for tag, raw in STACK_DTYPES]
 # ... and the lens distortion's own unit (its other kernels are instances of the register and drizzle units' templates)
 DISTORTION_UNITS = [('distortion', 'distortion', [])]
+# ... and the sky gradient's unit (its sample statistics are an instance of box_stats.h's kernel, which background.hip shares)
+GRADIENT_UNITS = [('gradient', 'gradient', [])]
 
 # -ffp-contract=off: the reference's NumPy expressions round after every operation, so no FMA
 # contraction anywhere; fused operations are written explicitly (fma()) where wanted.
@@ -57,7 +59,7 @@ def compile_units(obj_dir=OBJ):
     units += [('stack_inst_%s_%s_%s' % (tag, ctag, g), 'stack_inst',
                STACK_TU_FLAGS + ['-DAPGPU_INST_RAW=' + raw, '-DAPGPU_INST_CALIB=' + calib, '-DAPGPU_INST_GROUP=' + g])
               for g in STACK_GROUPS for tag, raw in STACK_DTYPES for ctag, calib in STACK_CALIB]
-    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS
+    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS + GRADIENT_UNITS
     for name, src, flags in units:
         stem = os.path.join(obj_dir, name)
         srcp = os.path.join(CSRC, src + '.hip')

@@ -37,6 +37,10 @@ STARLET_FORM = {'auto': 0, 'tile': 1, 'direct': 2}      # APGPU_STARLET_FORM_*
 DRIZZLE_TILE_H, DRIZZLE_TILE_W = 4, 64                  # APGPU_DRIZZLE_TILE_H, APGPU_DRIZZLE_TILE_W
 DEMOSAIC_RCD_TILE_H, DEMOSAIC_RCD_TILE_W, DEMOSAIC_RCD_HALO = 32, 64, 10     # APGPU_DEMOSAIC_RCD_TILE_H, _TILE_W, _HALO
 POLY_MAX_DEGREE = 5                                     # APGPU_POLY_MAX_DEGREE
+GRADIENT_MAX_SAMPLES, GRADIENT_MAX_RADIUS, GRADIENT_MAX_DEGREE = 4096, 32, 6     # APGPU_GRADIENT_MAX_SAMPLES, _MAX_RADIUS, _MAX_DEGREE
+GRADIENT_MIN_STEP, GRADIENT_MAX_STEP, GRADIENT_TILE_H, GRADIENT_TILE_W = 4, 64, 32, 128      # APGPU_GRADIENT_MIN_STEP, _MAX_STEP, _TILE_H, _TILE_W
+SURFACE_MODEL = {'poly': 0, 'tps': 1}                   # APGPU_SURFACE_POLY, APGPU_SURFACE_TPS
+GRADIENT_MODE = {'subtract': 0, 'divide': 1}            # APGPU_GRADIENT_SUBTRACT, APGPU_GRADIENT_DIVIDE
 
 
 class ApGpuError(RuntimeError):
@@ -204,6 +208,12 @@ SIGNATURES = {
                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     'apgpu_drizzle_reject_tiles_u8': (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                 C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'apgpu_sample_clipped_stats_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_double,
+                                                 C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_surface_lattice_f64': (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_surface_apply_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -3324,3 +3324,295 @@ def poly_input_tile_affines(maps, in_shape):
         a0, a1, a3, a4 = m.jacobian(px, py)
         o[...] = np.stack([a0, a1, (xc - a0 * px) - a1 * py, a3, a4, (yc - a3 * px) - a4 * py], axis=-1)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F20: removal of the large-scale sky gradient (csrc/gradient.hip; the rule restated in tests/gradient_model.py).
+# Device: the clipped statistics of the sample boxes, the surface on a lattice, the pass over the image.  Host: where the samples
+# lie and the robust fit of the surface to them (float64, numpy).
+GRADIENT_MODELS = tuple(_lib.SURFACE_MODEL)
+GRADIENT_MODES = tuple(_lib.GRADIENT_MODE)
+GRADIENT_MAX_SAMPLES, GRADIENT_MAX_RADIUS, GRADIENT_MAX_DEGREE = _lib.GRADIENT_MAX_SAMPLES, _lib.GRADIENT_MAX_RADIUS, _lib.GRADIENT_MAX_DEGREE
+GRADIENT_MIN_STEP, GRADIENT_MAX_STEP = _lib.GRADIENT_MIN_STEP, _lib.GRADIENT_MAX_STEP
+
+
+def _image_shape(shape):
+    H, W = (int(s) for s in shape)
+    if H < 1 or W < 1:
+        raise ValueError('the image shape must be positive, got %r' % (tuple(shape),))
+    return H, W
+
+
+def surface_frame(shape):
+    """(x0, y0, L) of the normalised coordinates u = (x - x0) / L, v = (y - y0) / L of an image [H, W]."""
+    H, W = _image_shape(shape)
+    return (W - 1) / 2.0, (H - 1) / 2.0, max(W, H) / 2.0
+
+
+def _centres(centres):
+    c = centres.cpu().numpy() if torch.is_tensor(centres) else np.asarray(centres)
+    if c.size == 0:
+        c = c.reshape(0, 2)
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise ValueError('centres must be [K, 2] (x, y), got shape %s' % (c.shape,))
+    if c.shape[0] > GRADIENT_MAX_SAMPLES:
+        raise ValueError('%d samples, at most %d' % (c.shape[0], GRADIENT_MAX_SAMPLES))
+    ci = np.rint(c).astype(np.int64)
+    if not np.array_equal(ci, c) or (ci.size and (ci.min() < -2 ** 31 or ci.max() >= 2 ** 31)):
+        raise ValueError('the centres must be whole pixels')
+    return np.ascontiguousarray(ci, np.int32)
+
+
+def _radius(radius):
+    r = int(radius)
+    if r != radius or not 0 <= r <= GRADIENT_MAX_RADIUS:
+        raise ValueError('the box radius must be a whole number in 0 .. %d, got %r' % (GRADIENT_MAX_RADIUS, radius))
+    return r
+
+
+def _step(step):
+    s = int(step)
+    if s != step or not GRADIENT_MIN_STEP <= s <= GRADIENT_MAX_STEP:
+        raise ValueError('the lattice step must be a whole number in %d .. %d, got %r' % (GRADIENT_MIN_STEP, GRADIENT_MAX_STEP, step))
+    return s
+
+
+def exclude_samples(xy, exclude=()):
+    """bool [K]: the centres xy [K, 2] (x, y) that lie in none of the `exclude` rectangles (x0, y0, x1, y1), bounds inclusive."""
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    keep = np.ones(len(xy), bool)
+    for rect in exclude:
+        if len(rect) != 4:
+            raise ValueError('an excluded rectangle is x0, y0, x1, y1, got %r' % (rect,))
+        x0, y0, x1, y1 = (float(t) for t in rect)
+        keep &= ~((xy[:, 0] >= min(x0, x1)) & (xy[:, 0] <= max(x0, x1)) & (xy[:, 1] >= min(y0, y1)) & (xy[:, 1] <= max(y0, y1)))
+    return keep
+
+
+def gradient_samples(shape, samples_per_row=16, exclude=()):
+    """Where the samples of an image [H, W] lie: int32 [K, 2] (x, y), a regular grid of samples_per_row columns with the same pitch
+    W / samples_per_row in y, centred in the image, row by row; without the centres inside one of the `exclude` rectangles
+    (x0, y0, x1, y1), bounds inclusive."""
+    H, W = _image_shape(shape)
+    n = int(samples_per_row)
+    if n != samples_per_row or n < 1:
+        raise ValueError('samples_per_row must be a whole number >= 1, got %r' % (samples_per_row,))
+    pitch = W / float(n)
+    rows = max(1, int(math.floor(H / pitch)))
+    if n * rows > GRADIENT_MAX_SAMPLES:
+        raise ValueError('%d x %d samples, at most %d' % (rows, n, GRADIENT_MAX_SAMPLES))
+    xs = np.floor((W - 1) / 2.0 + (np.arange(n) - (n - 1) / 2.0) * pitch + 0.5)
+    ys = np.floor((H - 1) / 2.0 + (np.arange(rows) - (rows - 1) / 2.0) * pitch + 0.5)
+    xy = np.stack([np.tile(xs, rows), np.repeat(ys, n)], axis=1)
+    return np.ascontiguousarray(xy[exclude_samples(xy, exclude)], np.int32)
+
+
+def sample_pixels(shape, centres, radius):
+    """int64 [K]: the pixels of each sample box that lie inside an image [H, W]."""
+    H, W = _image_shape(shape)
+    c, r = _centres(centres).astype(np.int64), _radius(radius)
+    nx = np.clip(np.minimum(c[:, 0] + r, W - 1) - np.maximum(c[:, 0] - r, 0) + 1, 0, None)
+    ny = np.clip(np.minimum(c[:, 1] + r, H - 1) - np.maximum(c[:, 1] - r, 0) + 1, 0, None)
+    return nx * ny
+
+
+def sample_clipped_stats(data, mask, centres, radius, sigma=3.0, maxiters=5):
+    """astropy's SigmaClip(sigma, maxiters) median / std of the square boxes of half-size `radius` (0 .. 32) about `centres` [K, 2]
+    (x, y; whole pixels, K <= 4096, anywhere - a box is clipped at the image edge): float64 device tensor [K, 4] = median, std,
+    survivors, pixels of the (2 radius + 1)^2 that were outside the image, masked (mask != 0) or not finite.  A box without a
+    survivor: NaN, NaN, 0.  The contract of box_clipped_stats, the boxes taken from a list; the std is np.nanstd of the survivors in the
+    box's row-major order, bit for bit."""
+    c, r = _centres(centres), _radius(radius)
+    if not float(sigma) >= 0.0 or int(maxiters) < 0:
+        raise ValueError('sigma must be >= 0 and maxiters >= 0, got %r, %r' % (sigma, maxiters))
+    data = _image_f32(data)
+    mask = _mask_u8(mask, data.shape, 'mask must have the image shape')
+    K = c.shape[0]
+    out = torch.empty((K, 4), dtype=torch.float64, device=data.device)
+    cd = torch.from_numpy(c).to(data.device)
+    check(_lib.load().apgpu_sample_clipped_stats_f32(_ptr(data), _ptr(mask), data.shape[0], data.shape[1], _ptr(cd) if K else None, K, r,
+                                                     float(sigma), int(maxiters), _ptr(out) if K else None, _stream()))
+    return out
+
+
+def _poly_terms(degree):
+    return [(t - j, j) for t in range(degree + 1) for j in range(t + 1)]
+
+
+def _poly_design(u, v, degree):
+    """[n, P]: u^i v^j in the coefficient order of the kernels (by total degree t, within t by j, i = t - j), the powers by repeated
+    multiplication."""
+    u, v = np.asarray(u, np.float64), np.asarray(v, np.float64)
+    pu, pv = [np.ones_like(u)], [np.ones_like(v)]
+    for _ in range(degree):
+        pu.append(pu[-1] * u)
+        pv.append(pv[-1] * v)
+    return np.stack([pu[i] * pv[j] for i, j in _poly_terms(degree)], axis=-1)
+
+
+def _tps_phi(q):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(q == 0.0, 0.0, 0.5 * q * np.log(q))
+
+
+def _surface_arg(surface):
+    if not isinstance(surface, dict) or surface.get('model') not in GRADIENT_MODELS:
+        raise ValueError('Unexpected surface model %r. Allowed models are: %s' % (surface.get('model') if isinstance(surface, dict) else surface,
+                                                                               list(GRADIENT_MODELS)))
+    x0, y0, L = (float(t) for t in surface['frame'])
+    if not (math.isfinite(x0) and math.isfinite(y0) and math.isfinite(L) and L > 0.0):
+        raise ValueError('the frame of a surface is finite x0, y0 and L > 0, got %r' % (surface['frame'],))
+    if surface['model'] == 'poly':
+        d = int(surface['degree'])
+        coef = np.ascontiguousarray(surface['coef'], np.float64).reshape(-1)
+        if not 1 <= d <= GRADIENT_MAX_DEGREE or coef.size != (d + 1) * (d + 2) // 2:
+            raise ValueError('a polynomial surface has a degree in 1 .. %d and (d + 1)(d + 2) / 2 coefficients, got degree %r and %d'
+                             % (GRADIENT_MAX_DEGREE, surface['degree'], coef.size))
+        return 'poly', (x0, y0, L), d, coef, None
+    a = np.asarray(surface['a'], np.float64).reshape(-1)
+    w = np.asarray(surface['w'], np.float64).reshape(-1)
+    uv = np.ascontiguousarray(surface['uv'], np.float64).reshape(-1, 2)
+    if a.size != 3 or uv.shape[0] != w.size or w.size > GRADIENT_MAX_SAMPLES:
+        raise ValueError('a thin-plate surface has a [3], w [K] and uv [K, 2] with K <= %d, got %d, %d and %s'
+                         % (GRADIENT_MAX_SAMPLES, a.size, w.size, uv.shape))
+    return 'tps', (x0, y0, L), w.size, np.ascontiguousarray(np.concatenate([a, w])), uv
+
+
+def surface_eval(surface, x, y):
+    """The surface itself (not its lattice interpolant) at pixel coordinates x, y, on the host in float64."""
+    kind, (x0, y0, L), n, params, uv = _surface_arg(surface)
+    u, v = (np.asarray(x, np.float64) - x0) / L, (np.asarray(y, np.float64) - y0) / L
+    if kind == 'poly':
+        return _poly_design(u, v, n) @ params
+    q = (u[..., None] - uv[:, 0]) ** 2 + (v[..., None] - uv[:, 1]) ** 2
+    return ((_tps_phi(q) @ params[3:] + params[0]) + params[1] * u) + params[2] * v
+
+
+def surface_lattice(surface, shape, step=16, device='cuda'):
+    """The surface at the nodes of the lattice of an image [H, W]: float64 device tensor [(H - 1) // step + 4, (W - 1) // step + 4],
+    node (iy, ix) at pixel ((ix - 1) step, (iy - 1) step) - every pixel has its 4 x 4 nodes, the model is analytic outside the
+    image.  surface: dict(model='poly', degree, coef, frame) or dict(model='tps', a, w, uv, frame), as fit_surface returns it."""
+    kind, (x0, y0, L), n, params, uv = _surface_arg(surface)
+    H, W = _image_shape(shape)
+    s = _step(step)
+    ny, nx = (H - 1) // s + 4, (W - 1) // s + 4
+    dev = torch.device(device)
+    p = torch.from_numpy(params).to(dev)
+    c = torch.from_numpy(uv).to(dev) if uv is not None and n else None
+    out = torch.empty((ny, nx), dtype=torch.float64, device=p.device)
+    check(_lib.load().apgpu_surface_lattice_f64(_lib.SURFACE_MODEL[kind], _ptr(p), _ptr(c), n, x0, y0, L, s, ny, nx, _ptr(out), _stream()))
+    return out
+
+
+def surface_apply(data, lattice, step=16, mode='subtract', pedestal=0.0, out=None, surface_out=None):
+    """One pass over a float32 image [H, W] with S the cubic-convolution interpolant (Keys, a = -1/2, float64) of `lattice` (float64
+    device tensor, from surface_lattice): 'subtract' out = float32(d - S + pedestal), 'divide' out = float32(d / S pedestal) and NaN
+    where S is not finite or <= 0; a pixel that is not finite stays NaN.  out may be data.  surface_out: None, True (a new plane) or a
+    float32 plane of its own for float32(S).  Returns out, or (out, surface) with surface_out."""
+    if mode not in GRADIENT_MODES:
+        raise ValueError('Unexpected mode %r. Allowed modes are: %s' % (mode, list(GRADIENT_MODES)))
+    s = _step(step)
+    data = _image_f32(data)
+    _need_cuda(lattice)
+    H, W = data.shape
+    ny, nx = (H - 1) // s + 4, (W - 1) // s + 4
+    if lattice.dtype != torch.float64 or tuple(lattice.shape) != (ny, nx):
+        raise ValueError('lattice must be a float64 tensor of shape %s for an image of %s at step %d, got %s %s'
+                         % ((ny, nx), (H, W), s, lattice.dtype, tuple(lattice.shape)))
+    if not math.isfinite(float(pedestal)):
+        raise ValueError('the pedestal must be finite, got %r' % (pedestal,))
+    lattice = lattice.contiguous()
+    out = _out_f32(out, data)
+    surf = None
+    if surface_out is not None and surface_out is not False:
+        surf = _out_f32(None if surface_out is True else surface_out, data, data, out, name='surface_out')
+    check(_lib.load().apgpu_surface_apply_f32(_ptr(data), _ptr(lattice), H, W, ny, nx, s, _lib.GRADIENT_MODE[mode], float(pedestal), _ptr(out),
+                                              _ptr(surf), _stream()))
+    return out if surf is None else (out, surf)
+
+
+def sample_sigmas(std, n):
+    """sigma_k = 1.2533 std / sqrt(n), the standard error of a median; a sample whose std is 0 (a single pixel, a constant box) takes
+    the smallest positive sigma of the others, 1 if there is none: its weight stays finite."""
+    std, n = np.asarray(std, np.float64), np.asarray(n, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        sg = 1.2533 * std / np.sqrt(n)
+    pos = np.isfinite(sg) & (sg > 0.0)
+    floor = sg[pos].min() if pos.any() else 1.0
+    return np.where(pos, sg, floor)
+
+
+def _fit_poly(u, v, z, om, degree):
+    A = _poly_design(u, v, degree)
+    sw = np.sqrt(om)
+    coef = np.linalg.lstsq(A * sw[:, None], z * sw, rcond=None)[0]
+    return coef, A @ coef
+
+
+def _fit_tps(u, v, z, om, smoothing):
+    n = u.size
+    Phi = _tps_phi((u[:, None] - u[None, :]) ** 2 + (v[:, None] - v[None, :]) ** 2)
+    T = np.stack([np.ones(n), u, v], axis=1)
+    M = np.zeros((n + 3, n + 3))
+    M[:n, :n] = Phi + np.diag(smoothing * n * om.mean() / om)
+    M[:n, n:] = T
+    M[n:, :n] = T.T
+    try:
+        sol = np.linalg.solve(M, np.concatenate([z, np.zeros(3)]))
+    except np.linalg.LinAlgError as exc:
+        raise ValueError('the thin-plate system is singular (samples on one line?): %s' % exc) from None
+    w, a = sol[:n], sol[n:]
+    return w, a, Phi @ w + T @ a
+
+
+def fit_surface(xy, values, sigmas, shape, model='poly', degree=3, smoothing=0.1, k_high=2.0, k_low=3.0, max_rounds=5, use=None):
+    """The robust fit of a surface to samples, on the host in float64.  xy [K, 2] pixel coordinates, values [K], sigmas [K] (> 0; the
+    weights are 1 / sigma^2), shape the image's, use [K] bool (None: every finite sample).
+      'poly'  total degree 1 .. 6 in u, v by weighted least squares
+      'tps'   S = a0 + a1 u + a2 v + sum w_k phi(q_k), phi = r^2 log r, with sum w = sum w u = sum w v = 0 and
+              smoothing n mean(omega) / omega_k on the diagonal (0 interpolates, a large value tends to the weighted plane)
+    After a fit sigma_r = 1.4826 median |r - median r| of the kept samples' residuals r = value - S; samples with r > k_high sigma_r
+    or r < -k_low sigma_r are dropped for good and the rest is fitted again, at most max_rounds times.  ValueError when fewer than
+    P + 3 samples (poly, P parameters) or 8 (tps) are left.
+    Returns (surface: a dict for surface_lattice / surface_eval, kept [K] bool, sigma_r of the last fit)."""
+    if model not in GRADIENT_MODELS:
+        raise ValueError('Unexpected model %r. Allowed models are: %s' % (model, list(GRADIENT_MODELS)))
+    frame = surface_frame(shape)
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    z, sg = np.asarray(values, np.float64).reshape(-1), np.asarray(sigmas, np.float64).reshape(-1)
+    if not (xy.shape[0] == z.size == sg.size):
+        raise ValueError('xy [K, 2], values [K] and sigmas [K] must agree, got %s, %d and %d' % (xy.shape, z.size, sg.size))
+    if model == 'poly':
+        d = int(degree)
+        if d != degree or not 1 <= d <= GRADIENT_MAX_DEGREE:
+            raise ValueError('the degree must be a whole number in 1 .. %d, got %r' % (GRADIENT_MAX_DEGREE, degree))
+        need = (d + 1) * (d + 2) // 2 + 3
+    else:
+        need = 8
+        if not float(smoothing) >= 0.0:
+            raise ValueError('the smoothing must be >= 0, got %r' % (smoothing,))
+    if not (float(k_high) > 0.0 and float(k_low) > 0.0) or int(max_rounds) < 0:
+        raise ValueError('k_high and k_low must be > 0 and max_rounds >= 0, got %r, %r, %r' % (k_high, k_low, max_rounds))
+    ok = np.isfinite(z) & np.isfinite(sg) & (sg > 0.0) & np.isfinite(xy).all(axis=1)
+    kept = ok if use is None else ok & np.asarray(use, bool).reshape(-1)
+    kept = kept.copy()
+    u, v = (xy[:, 0] - frame[0]) / frame[2], (xy[:, 1] - frame[1]) / frame[2]
+    om = np.zeros(z.size)
+    om[ok] = 1.0 / sg[ok] ** 2
+    for rnd in range(int(max_rounds) + 1):
+        idx = np.flatnonzero(kept)
+        if idx.size < need:
+            raise ValueError('%d samples are left, the %s surface needs at least %d' % (idx.size, model, need))
+        if model == 'poly':
+            coef, fit = _fit_poly(u[idx], v[idx], z[idx], om[idx], d)
+            surface = dict(model='poly', degree=d, coef=coef, frame=frame)
+        else:
+            w, a, fit = _fit_tps(u[idx], v[idx], z[idx], om[idx], float(smoothing))
+            surface = dict(model='tps', a=a, w=w, uv=np.stack([u[idx], v[idx]], axis=1), frame=frame, smoothing=float(smoothing))
+        res = z[idx] - fit
+        sigma_r = 1.4826 * float(np.median(np.abs(res - np.median(res))))
+        drop = (res > float(k_high) * sigma_r) | (res < -float(k_low) * sigma_r)
+        if rnd == int(max_rounds) or not sigma_r > 0.0 or not drop.any():
+            break
+        kept[idx[drop]] = False
+    return surface, kept, sigma_r

@@ -1089,6 +1089,62 @@ int apgpu_drizzle_reject_tiles_u8(const float *frames, int32_t n_frames, int64_t
                                   const float *ref, int64_t ref_height, int64_t ref_width, float k, float grow, uint8_t *mask_out,
                                   void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F20 Removal of the large-scale sky gradient of a co-add.  The reference has no such stage: this project's own
+ *     definition, restated in tests/gradient_model.py (PARITY UNPINNED).  Host side (ops.fit_surface): the robust fit of a surface
+ *     to a few hundred samples.  Device side: the samples, the surface on a lattice, and the pass over the image.  All surface
+ *     arithmetic is float64 and every operation rounds on its own.
+ *
+ *     Coordinates: pixel centre (x, y) = (column, row), 0-based; u = (x - x0) / L, v = (y - y0) / L; for an image of H x W the
+ *       callers pass x0 = (W - 1) / 2, y0 = (H - 1) / 2, L = max(W, H) / 2 (the convention of F19).
+ *
+ *     apgpu_sample_clipped_stats_f32: n_samples <= APGPU_GRADIENT_MAX_SAMPLES square boxes of half-size radius <= APGPU_GRADIENT_
+ *       MAX_RADIUS about centres [n_samples][2] (device int32: x, y; a centre may lie anywhere, outside the image too).  Per box
+ *       what apgpu_box_clipped_stats_f32 (F4) computes per mesh box - the same kernel, its origin taken from the list: SigmaClip(sigma,
+ *       maxiters, median / std) over the pixels that are inside the image, unmasked (mask NULL or mask == 0) and finite;
+ *       stats_out [n_samples][4] (device float64) = { median, std, count of the final survivors, pixels of the (2 radius + 1)^2
+ *       that were outside, masked or not finite }.  No survivor: NaN, NaN, 0.  n_samples == 0 launches nothing.  Unlike the mesh
+ *       entry point, whose std adds in a tree, the std here is np.nanstd of the final survivors with numpy's roundings: the sum from +0
+ *       in the box's row-major order, mean = sum / n, the squares of x - mean added in the same order, sqrt(q / n).
+ *     apgpu_surface_lattice_f64: the surface at the ny x nx nodes of a lattice of `step` pixels, node (iy, ix) at pixel ((ix - 1)
+ *       step, (iy - 1) step); lattice_out [ny][nx] device float64.
+ *         APGPU_SURFACE_POLY: n_terms = the degree d in 1 .. APGPU_GRADIENT_MAX_DEGREE; params [(d + 1)(d + 2) / 2] device float64,
+ *           coefficient k of u^i v^j in the order of F19 (t = 0 .. d, within t j = 0 .. t, i = t - j); powers by repeated
+ *           multiplication; S = the sum from +0 in coefficient order of c[k] (up[i] vp[j]).  centres_uv is not read.
+ *         APGPU_SURFACE_TPS: n_terms = K centres (0 .. APGPU_GRADIENT_MAX_SAMPLES); params [3 + K] = a0, a1, a2, w_0 .. w_{K-1};
+ *           centres_uv [K][2] = u_k, v_k.  q_k = (u - u_k)^2 + (v - v_k)^2 (the two squares, then their sum), phi(q) = 0 for q == 0,
+ *           else (0.5 q) log(q); S = ((A + a0) + a1 u) + a2 v with A the sum from +0 in index order of w_k phi(q_k).  The order is
+ *           fixed, so the same input gives the same bits; against another log the result differs by the roundings of K terms.
+ *     apgpu_surface_apply_f32: one pass over the image with S(x, y) the cubic-convolution interpolant (Keys, a = -1/2) of the lattice:
+ *         ix = x / step (integer), t = double(x - ix step) / double(step), the four nodes ix .. ix + 3 with the weights
+ *           w0 = ((-0.5 t + 1) t - 0.5) t, w1 = (1.5 t - 2.5) t t + 1, w2 = ((-1.5 t + 2) t + 0.5) t, w3 = (0.5 t - 0.5) t t;
+ *         per lattice row R_a = ((w0 n[a][0] + w1 n[a][1]) + w2 n[a][2]) + w3 n[a][3], then S the same expression of the row weights
+ *           and R_0 .. R_3.  ny = (height - 1) / step + 4 and nx likewise (anything else: APGPU_EINVAL): every pixel has its 4 x 4 nodes.
+ *         APGPU_GRADIENT_SUBTRACT: out = float32((double(d) - S) + pedestal).
+ *         APGPU_GRADIENT_DIVIDE:   out = float32((double(d) / S) pedestal), NaN where S is not finite or S <= 0.
+ *         A non-finite d gives NaN in both modes.  surface_out (may be NULL): float32(S) at every pixel.  out may be data;
+ *         surface_out must be a plane of its own.  16-byte loads and stores when the planes are 16-byte aligned and width % 4 == 0.
+ *     APGPU_EINVAL: NULL or misaligned pointers, a step outside APGPU_GRADIENT_MIN_STEP .. APGPU_GRADIENT_MAX_STEP, more samples or
+ *       a larger radius or degree than the limits, sigma < 0 or NaN, an unknown model or mode, a NaN pedestal.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_GRADIENT_MAX_SAMPLES 4096
+#define APGPU_GRADIENT_MAX_RADIUS 32
+#define APGPU_GRADIENT_MAX_DEGREE 6
+#define APGPU_GRADIENT_MIN_STEP 4
+#define APGPU_GRADIENT_MAX_STEP 64
+#define APGPU_GRADIENT_TILE_H 32
+#define APGPU_GRADIENT_TILE_W 128
+#define APGPU_SURFACE_POLY 0
+#define APGPU_SURFACE_TPS 1
+#define APGPU_GRADIENT_SUBTRACT 0
+#define APGPU_GRADIENT_DIVIDE 1
+int apgpu_sample_clipped_stats_f32(const float *data, const uint8_t *mask, int64_t height, int64_t width, const int32_t *centres,
+                                   int32_t n_samples, int32_t radius, double sigma, int32_t maxiters, double *stats_out, void *stream);
+int apgpu_surface_lattice_f64(int32_t model, const double *params, const double *centres_uv, int32_t n_terms, double x0, double y0,
+                              double half_size, int32_t step, int32_t ny, int32_t nx, double *lattice_out, void *stream);
+int apgpu_surface_apply_f32(const float *data, const double *lattice, int64_t height, int64_t width, int32_t ny, int32_t nx,
+                            int32_t step, int32_t mode, double pedestal, float *out, float *surface_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
