@@ -31,6 +31,7 @@ _LAZY = {
     'ApMultiscale': ('.core.ApMultiscale', 'ApMultiscale'),
     'ApDrizzle': ('.core.ApDrizzle', 'ApDrizzle'),
     'ApRemoveGradient': ('.core.ApRemoveGradient', 'ApRemoveGradient'),
+    'ApAstrometry': ('.core.ApAstrometry', 'ApAstrometry'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

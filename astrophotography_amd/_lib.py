@@ -41,6 +41,7 @@ GRADIENT_MAX_SAMPLES, GRADIENT_MAX_RADIUS, GRADIENT_MAX_DEGREE = 4096, 32, 6    
 GRADIENT_MIN_STEP, GRADIENT_MAX_STEP, GRADIENT_TILE_H, GRADIENT_TILE_W = 4, 64, 32, 128      # APGPU_GRADIENT_MIN_STEP, _MAX_STEP, _TILE_H, _TILE_W
 SURFACE_MODEL = {'poly': 0, 'tps': 1}                   # APGPU_SURFACE_POLY, APGPU_SURFACE_TPS
 GRADIENT_MODE = {'subtract': 0, 'divide': 1}            # APGPU_GRADIENT_SUBTRACT, APGPU_GRADIENT_DIVIDE
+CELL_MAX_CAPACITY = 65536                               # APGPU_CELL_MAX_CAPACITY
 
 
 class ApGpuError(RuntimeError):
@@ -214,6 +215,10 @@ SIGNATURES = {
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'apgpu_surface_apply_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_sky_project': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    'apgpu_cell_select': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
 }
 
 _lib = None

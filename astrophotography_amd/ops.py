@@ -3616,3 +3616,262 @@ def fit_surface(xy, values, sigmas, shape, model='poly', degree=3, smoothing=0.1
             break
         kept[idx[drop]] = False
     return surface, kept, sigma_r
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F21: ApAstrometry - offline plate solving against a catalogue (csrc/astrometry.hip; astrometry.net absent, parity unpinned)
+SOLVE_NOMINAL, SOLVE_NO_SOLUTION = 0, 2
+
+
+def _f64_dev(a, name):
+    t = torch.as_tensor(a)
+    if t.dim() != 1:
+        raise ValueError('%s must be one-dimensional, got shape %s' % (name, tuple(t.shape)))
+    return t.to(device=t.device if t.is_cuda else 'cuda', dtype=torch.float64).contiguous()
+
+
+def sky_project(ra, dec, centre, cos_rc=-1.0):
+    """The standard coordinates (xi, eta: degrees, xi towards east; NaN behind the tangent plane) of stars (ra, dec: degrees, float64
+    [n]) about centre = (ra0, dec0), with wcs.TanWcs.sky2pix's expressions in its order, and keep (uint8): 1 where ra and dec are
+    finite, the star is in front of the plane and cos(its distance from the centre) >= cos_rc.  Device tensors."""
+    ra, dec = _f64_dev(ra, 'ra'), _f64_dev(dec, 'dec')
+    if ra.shape != dec.shape:
+        raise ValueError('ra and dec must have one length, got %d and %d' % (ra.numel(), dec.numel()))
+    n = int(ra.numel())
+    xi, eta = torch.empty(n, dtype=torch.float64, device=ra.device), torch.empty(n, dtype=torch.float64, device=ra.device)
+    keep = torch.empty(n, dtype=torch.uint8, device=ra.device)
+    check(_lib.load().apgpu_sky_project(_ptr(ra), _ptr(dec), n, float(centre[0]), float(centre[1]), float(cos_rc), _ptr(xi), _ptr(eta),
+                                        _ptr(keep), _stream()))
+    return xi, eta, keep
+
+
+def cell_select(x, y, cells, capacity=512):
+    """Per cell (cells [C, 3] = centre x, centre y, half side) the first `capacity` stars of the list (x, y float64 [n], brightest
+    first) inside the closed square |x - cx| <= half, |y - cy| <= half.  Returns (idx int32 [C, capacity]: ascending star indices,
+    -1 in the unused slots; count int32 [C]; inside int32 [C]: the number of stars in the square where that is <= capacity, else
+    some value above it).  Exact and the same on every run.  Device tensors."""
+    x, y = _f64_dev(x, 'x'), _f64_dev(y, 'y')
+    if x.shape != y.shape:
+        raise ValueError('x and y must have one length, got %d and %d' % (x.numel(), y.numel()))
+    cells = torch.as_tensor(np.asarray(cells.cpu() if torch.is_tensor(cells) else cells, np.float64).reshape(-1, 3)).to(x.device).contiguous()
+    capacity = int(capacity)
+    if not 1 <= capacity <= _lib.CELL_MAX_CAPACITY:
+        raise ValueError('capacity = %d is outside 1 .. %d' % (capacity, _lib.CELL_MAX_CAPACITY))
+    C_ = int(cells.shape[0])
+    idx = torch.empty((C_, capacity), dtype=torch.int32, device=x.device)
+    count, inside = torch.empty(C_, dtype=torch.int32, device=x.device), torch.empty(C_, dtype=torch.int32, device=x.device)
+    check(_lib.load().apgpu_cell_select(_ptr(x), _ptr(y), int(x.numel()), _ptr(cells), C_, capacity, _ptr(idx), _ptr(count), _ptr(inside),
+                                        _stream()))
+    return idx, count, inside
+
+
+def scale_levels(ratio):
+    """The cell sides of the plate solver relative to min(nx, ny): geometric from 1 / ratio to ratio, 1 + 2 ceil(ln ratio / ln 1.3) of them."""
+    m = int(math.ceil(math.log(ratio) / math.log(1.3) - 1e-9)) if ratio > 1.0 else 0
+    return [float(ratio) ** ((k - m) / m) if m else 1.0 for k in range(2 * m + 1)]
+
+
+def astrometry_cells(shape, scale, ratio, radius):
+    """The search cells [C, 3] = (cx, cy, half side) in nominal pixels, and cos(Rc) of the catalogue cut."""
+    ny, nx = shape
+    r_px = radius * 3600.0 / scale
+    out = []
+    levels = scale_levels(ratio)
+    for f in levels:
+        L = f * min(nx, ny)
+        stride = L / 2.0
+        m = int(math.ceil(r_px / stride))
+        out += [(ix * stride, iy * stride, L / 2.0) for iy in range(-m, m + 1) for ix in range(-m, m + 1)]
+    rc = radius * math.sqrt(2.0) + (max(levels) * min(nx, ny) / 2.0) * math.sqrt(2.0) * scale / 3600.0
+    return np.array(out, np.float64).reshape(-1, 3), math.cos(min(rc, 89.0) * math.pi / 180.0)
+
+
+def _std_coords(ra, dec, crval):
+    """Standard coordinates (degrees) about crval on the host: wcs.TanWcs.sky2pix's expressions."""
+    r = math.pi / 180.0
+    a, d, a0, d0 = ra * r, dec * r, np.float64(crval[0]) * r, np.float64(crval[1]) * r
+    with np.errstate(divide='ignore', invalid='ignore'):
+        cosc = np.sin(d0) * np.sin(d) + np.cos(d0) * np.cos(d) * np.cos(a - a0)
+        xi = np.where(cosc > 0, np.cos(d) * np.sin(a - a0) / cosc, np.nan) / r
+        eta = np.where(cosc > 0, (np.cos(d0) * np.sin(d) - np.sin(d0) * np.cos(d) * np.cos(a - a0)) / cosc, np.nan) / r
+    return xi, eta
+
+
+def _std_sky(xi, eta, crval):
+    """... and back: wcs.TanWcs.pix2sky's."""
+    r = math.pi / 180.0
+    x, e, a0, d0 = np.float64(xi) * r, np.float64(eta) * r, np.float64(crval[0]) * r, np.float64(crval[1]) * r
+    den = np.cos(d0) - e * np.sin(d0)
+    ra = a0 + np.arctan2(x, den)
+    dec = np.arctan2((e * np.cos(d0) + np.sin(d0)) * np.cos(ra - a0), den)
+    return float(np.mod(ra / r, 360.0)), float(dec / r)
+
+
+def _pair_rms(w, xy, ra, dec):
+    px, py = w.sky2pix(ra, dec)
+    return float(np.sqrt(np.mean((px - xy[:, 0]) ** 2 + (py - xy[:, 1]) ** 2)))
+
+
+def tan_fit(xy, ra, dec, crpix, crval, max_iter=10, tol=1e-11):
+    """The least-squares TAN WCS with the given CRPIX (FITS, 1-based) through pairs (pixel xy [n, 2], 0-based; ra, dec degrees),
+    from the start CRVAL: project about CRVAL, fit xi and eta as affine functions of the offset from CRPIX, move CRVAL to the sky
+    position of the constant terms, until they are below `tol` degrees.  Host float64.  -> (wcs.TanWcs, 2-D rms in pixels)."""
+    from .wcs import TanWcs
+    xy = np.asarray(xy, np.float64).reshape(-1, 2)
+    ra, dec = np.asarray(ra, np.float64), np.asarray(dec, np.float64)
+    u, v = xy[:, 0] + 1.0 - crpix[0], xy[:, 1] + 1.0 - crpix[1]
+    D = np.stack([u, v, np.ones_like(u)], axis=1)
+    crval = (float(crval[0]), float(crval[1]))
+    for _ in range(max_iter):
+        xi, eta = _std_coords(ra, dec, crval)
+        cx, cy = np.linalg.lstsq(D, xi, rcond=None)[0], np.linalg.lstsq(D, eta, rcond=None)[0]
+        crval = _std_sky(cx[2], cy[2], crval)
+        if math.hypot(cx[2], cy[2]) < tol:
+            break
+    w = TanWcs(crpix, crval, [[cx[0], cx[1]], [cy[0], cy[1]]])
+    return w, _pair_rms(w, xy, ra, dec)
+
+
+_SIP2, _SIP_INV = ((2, 0), (1, 1), (0, 2)), ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2))
+
+
+def _sip_fit(xy, ra, dec, tan, shape, rounds=2):
+    """A, B of order 2 on top of `tan`, alternated with the TAN fit; AP, BP from a 16 x 16 grid."""
+    from .wcs import SipWcs
+    design = lambda p, q, terms: np.stack([p ** i * q ** j for i, j in terms], axis=1)
+    crpix = (float(tan.crpix[0]), float(tan.crpix[1]))
+    u, v = xy[:, 0] + 1.0 - crpix[0], xy[:, 1] + 1.0 - crpix[1]
+    D, Dall = design(u, v, _SIP2), design(u, v, _SIP_INV)
+    for _ in range(rounds):
+        xi, eta = _std_coords(ra, dec, tan.crval)
+        U = tan.cdinv[0, 0] * xi + tan.cdinv[0, 1] * eta
+        V = tan.cdinv[1, 0] * xi + tan.cdinv[1, 1] * eta
+        a = np.linalg.lstsq(Dall, U - u, rcond=None)[0][3:]                 # the constant and linear terms are the next TAN fit's
+        b = np.linalg.lstsq(Dall, V - v, rcond=None)[0][3:]
+        tan, _ = tan_fit(np.stack([xy[:, 0] + D @ a, xy[:, 1] + D @ b], axis=1), ra, dec, crpix, tan.crval)
+    ny, nx = shape
+    gx, gy = np.meshgrid(np.linspace(0.0, nx - 1.0, 16), np.linspace(0.0, ny - 1.0, 16))
+    gu, gv = gx.ravel() + 1.0 - crpix[0], gy.ravel() + 1.0 - crpix[1]
+    G = design(gu, gv, _SIP2)
+    fu, fv = gu + G @ a, gv + G @ b
+    Di = design(fu, fv, _SIP_INV)
+    ap, bp = np.linalg.lstsq(Di, gu - fu, rcond=None)[0], np.linalg.lstsq(Di, gv - fv, rcond=None)[0]
+    w = SipWcs(crpix, tan.crval, tan.cd, dict(zip(_SIP2, a)), dict(zip(_SIP2, b)), dict(zip(_SIP_INV, ap)), dict(zip(_SIP_INV, bp)))
+    return w, _pair_rms(w, xy, ra, dec)
+
+
+def _solve_rematch(w, xy, ra, dec, shape, match_radius, rms, fit, max_rounds=4):
+    """mutual nearest neighbours of the image's stars and the catalogue's stars under the current WCS."""
+    ny, nx = shape
+    M = _lib.REGISTER_MAX_STARS
+    pairs = None
+    for rnd in range(max_rounds):
+        radius = float(match_radius) if rnd == 0 else float(np.clip(3.0 * rms, 0.5, match_radius))
+        px, py = w.sky2pix(ra, dec)
+        with np.errstate(invalid='ignore'):
+            near = np.flatnonzero((px >= -3.0) & (px <= nx - 1.0 + 3.0) & (py >= -3.0) & (py <= ny - 1.0 + 3.0))[:M]
+        lists = [xy[:M], np.stack([px[near], py[near]], axis=1)]
+        both = np.zeros((2, max(1, len(lists[0]), len(lists[1])), 2))
+        for f, a in enumerate(lists):
+            both[f, :len(a)] = a
+        nm = nearest_match(both, [len(a) for a in lists], np.tile(np.asarray(REGISTER_IDENTITY), (2, 1)), radius)
+        fwd, bwd = nm['fwd_idx'][1].cpu().numpy(), nm['bwd_idx'][1].cpu().numpy()
+        i = np.nonzero(fwd >= 0)[0]
+        i = i[bwd[fwd[i]] == i]
+        new = np.stack([i, near[fwd[i]]], axis=1).astype(np.int64)
+        if pairs is not None and np.array_equal(new, pairs):
+            break
+        pairs = new
+        if len(pairs) < 3:
+            break
+        w, rms = fit(xy[pairs[:, 0]], ra[pairs[:, 1]], dec[pairs[:, 1]], w)
+    return w, rms, pairs
+
+
+def solve_field(xy, shape, catalogue, centre, scale, scale_err_ratio=1.3, radius=1.0, K=40, cell_stars=512, n_cand=5, match_radius=3.0,
+                min_matched=10, use_sip=False):
+    """Plate-solves one frame against a catalogue, given a hint.  xy [n, 2]: the image's stars, 0-based pixels, brightest
+    first; shape (ny, nx); catalogue: a mapping with 'ra', 'dec' (degrees) and 'mag' (arrays or tensors of one length; rows with a
+    non-finite value are dropped); centre (ra0, dec0): the hint; scale: the nominal arcsec per pixel, good to the factor
+    scale_err_ratio; radius: how far (degrees) the true centre may be from the hint.
+
+    The catalogue is projected about the hint (sky_project), put in brightness order and cut into overlapping square cells of a few
+    sizes (cell_select); every cell's brightest K stars vote against the image's (triangle_build / triangle_vote with mirrored
+    triangles allowed); the n_cand cells with the most votes are registered (register_lists); from the best candidate a TAN WCS is
+    fitted on the sphere, refined by rematching all of the image's stars with all of the catalogue's (nearest_match), with SIP terms of
+    order 2 when use_sip.  The fits are host float64.
+
+    Returns a dict: status (SOLVE_NOMINAL or SOLVE_NO_SOLUTION: a status, not an error), wcs (wcs.TanWcs / wcs.SipWcs or None), pairs
+    [n, 2] (image star, catalogue row), n_matched, rms (pixels), scale (arcsec / pixel), cell (the winning cell), cell_scale (true /
+    nominal scale of its registration), parity (+1: east left of north as on the sky, -1 mirrored; 0 unsolved), n_seed, peak_votes
+    [C], cells [C, 3] and candidates (a dict per registered cell)."""
+    xy = np.asarray(xy.cpu() if torch.is_tensor(xy) else xy, np.float64).reshape(-1, 2)
+    ny, nx = int(shape[0]), int(shape[1])
+    scale, ratio = float(scale), float(scale_err_ratio)
+    if not (scale > 0.0 and ratio >= 1.0 and radius > 0.0 and nx > 0 and ny > 0):
+        raise ValueError('solve_field: scale and radius must be positive and scale_err_ratio >= 1')
+    cells, cos_rc = astrometry_cells((ny, nx), scale, ratio, float(radius))
+    ra, dec, mag = (_f64_dev(catalogue[k], k) for k in ('ra', 'dec', 'mag'))
+    if not ra.shape == dec.shape == mag.shape:
+        raise ValueError('solve_field: the catalogue columns must have one length')
+    rows = torch.nonzero(torch.isfinite(ra) & torch.isfinite(dec) & torch.isfinite(mag)).reshape(-1)
+    xi, eta, keep = sky_project(ra[rows], dec[rows], centre, cos_rc)
+    kept = torch.nonzero(keep).reshape(-1)
+    order = torch.sort(mag[rows][kept], stable=True)[1]
+    kept = kept[order]
+    rows = rows[kept]
+    X, Y = (-xi[kept]) * 3600.0 / scale, eta[kept] * 3600.0 / scale
+    idx, count, _ = cell_select(X, Y, cells, cell_stars)
+    half = min(nx, ny) / 2.0
+    with np.errstate(invalid='ignore'):
+        f0 = np.flatnonzero((np.abs(xy[:, 0] - (nx - 1) / 2.0) <= half) & (np.abs(xy[:, 1] - (ny - 1) / 2.0) <= half))[:cell_stars]
+    C_ = len(cells)
+    fxy = torch.zeros((1 + C_, int(cell_stars), 2), dtype=torch.float64, device=X.device)
+    fxy[0, :len(f0)] = torch.from_numpy(xy[f0]).to(X.device)
+    if C_ and X.numel():
+        g = idx.clamp(min=0).long()
+        fxy[1:] = torch.where((idx >= 0)[..., None], torch.stack([X[g], Y[g]], dim=-1), fxy[1:])
+    fcount = torch.cat([torch.tensor([len(f0)], dtype=torch.int32, device=X.device), count])
+    votes = triangle_vote(triangle_build(fxy, fcount, K, 5.0), 0.002, True)
+    peak = votes[1:].reshape(C_, -1).amax(dim=1).cpu().numpy() if C_ else np.zeros(0, np.int32)
+    out = dict(status=SOLVE_NO_SOLUTION, wcs=None, pairs=np.zeros((0, 2), np.int64), n_matched=0, rms=np.nan, scale=np.nan, cell=-1,
+               cell_scale=np.nan, parity=0, n_seed=0, peak_votes=peak, cells=cells, candidates=[])
+    best = None
+    lo, hi = 1.0 / (1.02 * ratio), 1.02 * ratio
+    for c in np.argsort(-peak.astype(np.int64), kind='stable')[:n_cand]:
+        if peak[c] <= 0:
+            continue
+        sel = torch.tensor([0, 1 + int(c)], device=X.device)
+        r = register_lists(fxy[sel], fcount[sel], K, 0.002, 5.0, match_radius, 'affine', True)
+        cand = dict(cell=int(c), ok=bool(r['ok'][1]), n_matched=int(r['n_matched'][1]), n_seed=int(r['n_seed'][1]), coeffs=r['coeffs'][1],
+                    pairs=r['pairs'][1], scale=np.nan, counted=False)
+        if cand['ok']:
+            A = cand['coeffs']
+            cand['scale'] = float(np.sqrt(abs(A[0] * A[4] - A[1] * A[3])))
+            cand['counted'] = bool(lo <= cand['scale'] <= hi)
+        out['candidates'].append(cand)
+        if cand['counted'] and (best is None or (cand['n_matched'], -cand['cell']) > (best['n_matched'], -best['cell'])):
+            best = cand
+    if best is None:
+        return out
+    A = best['coeffs']
+    out.update(cell=best['cell'], cell_scale=best['scale'], n_seed=best['n_seed'], parity=1 if A[0] * A[4] - A[1] * A[3] > 0 else -1)
+    crpix = ((nx + 1) / 2.0, (ny + 1) / 2.0)
+    c0 = _register_apply(A, np.array([[(nx - 1) / 2.0, (ny - 1) / 2.0]]))[0]
+    crval = _std_sky(-c0[0] * scale / 3600.0, c0[1] * scale / 3600.0, (float(centre[0]), float(centre[1])))
+    ra_k, dec_k = ra[rows].cpu().numpy(), dec[rows].cpu().numpy()
+    cat = idx[best['cell']].cpu().numpy()[best['pairs'][:, 1]]
+    w, rms = tan_fit(xy[f0[best['pairs'][:, 0]]], ra_k[cat], dec_k[cat], crpix, crval)
+    fit = lambda p, a, d, w0: tan_fit(p, a, d, crpix, w0.crval)
+    w, rms, pairs = _solve_rematch(w, xy, ra_k, dec_k, (ny, nx), match_radius, rms, fit)
+    if use_sip and len(pairs) >= 12:
+        sfit = lambda p, a, d, w0: _sip_fit(p, a, d, w0.tan(), (ny, nx))
+        w, rms = sfit(xy[pairs[:, 0]], ra_k[pairs[:, 1]], dec_k[pairs[:, 1]], w)
+        w, rms, pairs = _solve_rematch(w, xy, ra_k, dec_k, (ny, nx), match_radius, rms, sfit, max_rounds=1)
+    fitted = 3600.0 * float(np.sqrt(abs(np.linalg.det(w.cd))))
+    rows_h = rows.cpu().numpy()
+    out.update(wcs=w, rms=rms, n_matched=len(pairs), scale=fitted,
+               pairs=np.stack([pairs[:, 0], rows_h[pairs[:, 1]]], axis=1) if len(pairs) else out['pairs'])
+    if len(pairs) >= min_matched and scale / (1.02 * ratio) <= fitted <= scale * 1.02 * ratio and len(pairs) >= best['n_seed']:
+        out['status'] = SOLVE_NOMINAL
+    return out

@@ -146,6 +146,17 @@ class SipWcs:
     def tan(self):
         return self._tan
 
+    def header_cards(self):
+        """The cards `from_header` reads back: the TAN cards with CTYPE = ...-SIP, the orders and every non-zero coefficient."""
+        cards = dict(self._tan.header_cards(), CTYPE1='RA---TAN-SIP', CTYPE2='DEC--TAN-SIP')
+        for prefix, t, lowest in (('A', self.a, 2), ('B', self.b, 2), ('AP', self.ap, 0), ('BP', self.bp, 0)):
+            if t is None:
+                continue
+            cards[prefix + '_ORDER'] = max([p + q for p, q in t] + [lowest])
+            for (p, q), c in sorted(t.items()):
+                cards['%s_%d_%d' % (prefix, p, q)] = float(c)
+        return cards
+
     @staticmethod
     def _poly(t, u, v, du=0, dv=0):
         s = np.zeros(np.broadcast(u, v).shape)

@@ -38,7 +38,8 @@ extern "C" {
                                        apgpu_bayer_demosaic, apgpu_bayer_channel_sums;
                                        apgpu_drizzle_f32, apgpu_drizzle_reject_u8;
                                        apgpu_nearest_match_poly, apgpu_poly_tile_affines, apgpu_drizzle_tiles_f32,
-                                       apgpu_drizzle_reject_tiles_u8 */
+                                       apgpu_drizzle_reject_tiles_u8;
+                                       apgpu_sky_project, apgpu_cell_select */
 
 /* error codes */
 #define APGPU_OK            0
@@ -1144,6 +1145,37 @@ int apgpu_surface_lattice_f64(int32_t model, const double *params, const double 
                               double half_size, int32_t step, int32_t ny, int32_t nx, double *lattice_out, void *stream);
 int apgpu_surface_apply_f32(const float *data, const double *lattice, int64_t height, int64_t width, int32_t ny, int32_t nx,
                             int32_t step, int32_t mode, double pedestal, float *out, float *surface_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * F21 Offline plate solving against a catalogue.  The reference sends its source list to astrometry.net; this is the
+ *     project's own definition, restated in tests/astrometry_model.py (PARITY UNPINNED).  Device side: the catalogue's projection
+ *     about the hint and its search cells.  The triangle votes and neighbour searches are F8's; the fits are host float64.
+ *     All arithmetic float64, every operation rounds on its own.
+ *
+ *     apgpu_sky_project: standard coordinates of n stars (ra, dec: device float64, degrees) about (ra0, dec0), the expressions of
+ *       the gnomonic projection in this order, with r = pi / 180 and a = ra r, d = dec r, a0 = ra0 r, d0 = dec0 r:
+ *         cosc = sin d0 sin d + (cos d0 cos d) cos(a - a0)
+ *         xi   = ((cos d sin(a - a0)) / cosc) / r
+ *         eta  = ((cos d0 sin d - (sin d0 cos d) cos(a - a0)) / cosc) / r
+ *       xi, eta (device float64 [n], degrees) are NaN where cosc > 0 does not hold (behind the tangent plane, or a non-finite
+ *       input); keep (device uint8 [n]) = 1 iff ra and dec are finite, cosc > 0 and cosc >= cos_rc.  keep may be NULL.  One lane
+ *       per star; n == 0 launches nothing.
+ *     apgpu_cell_select: for each of n_cells closed squares (cells: device float64 [n_cells][3] = centre x, centre y, half side)
+ *       the indices of the first `capacity` of the n stars (x, y: device float64 [n], in the caller's order - brightest first) with
+ *       |x - cx| <= half and |y - cy| <= half (NaN coordinates are in no cell).  idx [n_cells][capacity] int32: those indices in
+ *       ascending order, the unused slots -1; inside [n_cells]: the number of stars in the square when that is <= capacity, else
+ *       some value > capacity (the scan stops once the list is full and one more star was seen); count [n_cells] = min(capacity,
+ *       inside).  An ordered compaction - a workgroup per cell, wave ballots and prefix counts, no atomics: the same bytes on
+ *       every run.  n_cells == 0 launches nothing; n == 0 writes empty lists (x and y are then not read and may be NULL).
+ *     APGPU_EINVAL: NULL or misaligned pointers, n or n_cells outside 0 .. 2^31 - 1, capacity outside 1 .. APGPU_CELL_MAX_CAPACITY,
+ *       n_cells * capacity >= 2^31, a non-finite (ra0, dec0) or |dec0| > 90, cos_rc outside -1 .. 1.  A cell with a non-finite
+ *       member holds no star.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_CELL_MAX_CAPACITY 65536
+int apgpu_sky_project(const double *ra, const double *dec, int64_t n, double ra0, double dec0, double cos_rc, double *xi, double *eta,
+                      uint8_t *keep, void *stream);
+int apgpu_cell_select(const double *x, const double *y, int64_t n, const double *cells, int64_t n_cells, int32_t capacity, int32_t *idx,
+                      int32_t *count, int32_t *inside, void *stream);
 
 #ifdef __cplusplus
 }
