@@ -32,6 +32,7 @@ _LAZY = {
     'ApDrizzle': ('.core.ApDrizzle', 'ApDrizzle'),
     'ApRemoveGradient': ('.core.ApRemoveGradient', 'ApRemoveGradient'),
     'ApAstrometry': ('.core.ApAstrometry', 'ApAstrometry'),
+    'ApEmpiricalPsf': ('.core.ApEmpiricalPsf', 'ApEmpiricalPsf'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

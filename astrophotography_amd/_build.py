@@ -36,6 +36,8 @@ DISTORTION_UNITS = [('distortion', 'distortion', [])]
 GRADIENT_UNITS = [('gradient', 'gradient', [])]
 # ... and the plate solver's catalogue kernels (its votes and neighbour searches are the register unit's)
 ASTROMETRY_UNITS = [('astrometry', 'astrometry', [])]
+# ... and the empirical PSF's unit (its interpolant: epsf_core.h)
+EPSF_UNITS = [('epsf', 'epsf', [])]
 
 # -ffp-contract=off: the reference's NumPy expressions round after every operation, so no FMA
 # contraction anywhere; fused operations are written explicitly (fma()) where wanted.
@@ -61,7 +63,7 @@ def compile_units(obj_dir=OBJ):
     units += [('stack_inst_%s_%s_%s' % (tag, ctag, g), 'stack_inst',
                STACK_TU_FLAGS + ['-DAPGPU_INST_RAW=' + raw, '-DAPGPU_INST_CALIB=' + calib, '-DAPGPU_INST_GROUP=' + g])
               for g in STACK_GROUPS for tag, raw in STACK_DTYPES for ctag, calib in STACK_CALIB]
-    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS + GRADIENT_UNITS + ASTROMETRY_UNITS
+    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS + GRADIENT_UNITS + ASTROMETRY_UNITS + EPSF_UNITS
     for name, src, flags in units:
         stem = os.path.join(obj_dir, name)
         srcp = os.path.join(CSRC, src + '.hip')

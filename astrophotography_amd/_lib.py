@@ -42,6 +42,7 @@ GRADIENT_MIN_STEP, GRADIENT_MAX_STEP, GRADIENT_TILE_H, GRADIENT_TILE_W = 4, 64, 
 SURFACE_MODEL = {'poly': 0, 'tps': 1}                   # APGPU_SURFACE_POLY, APGPU_SURFACE_TPS
 GRADIENT_MODE = {'subtract': 0, 'divide': 1}            # APGPU_GRADIENT_SUBTRACT, APGPU_GRADIENT_DIVIDE
 CELL_MAX_CAPACITY = 65536                               # APGPU_CELL_MAX_CAPACITY
+EPSF_MAX_OVERSAMPLING, EPSF_MAX_RADIUS, EPSF_REC, EPSF_TILE = 4, 32, 8, 32      # APGPU_EPSF_MAX_OVERSAMPLING, _MAX_RADIUS, _REC, _TILE
 
 
 class ApGpuError(RuntimeError):
@@ -219,6 +220,15 @@ SIGNATURES = {
                                     C.c_void_p]),
     'apgpu_cell_select': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    'apgpu_epsf_accumulate_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_epsf_update_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                        C.c_void_p, C.c_void_p]),
+    'apgpu_epsf_shift_f32': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    'apgpu_epsf_fit_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    'apgpu_epsf_render_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

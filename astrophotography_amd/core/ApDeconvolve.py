@@ -8,7 +8,7 @@ between ap_coadd and ap_composite: the input is a float32 image, NaN meaning "no
           FITS decode and encode
   host    the PSF stamp (a pixel-integrated Gaussian or Moffat of the measured FWHM, or a stamp from a file), headers
 
-Out of scope: an empirical PSF built from the stars, spatially varying PSFs, deringing or star protection, TV or wavelet
+Out of scope (the empirical PSF of the stars is ApEmpiricalPsf; its file is a stamp file for `psf`): spatially varying PSFs, deringing or star protection, TV or wavelet
 regularisation, PSFs of radius above 12 (bin the image).
 """
 import math

@@ -3875,3 +3875,291 @@ def solve_field(xy, shape, catalogue, centre, scale, scale_err_ratio=1.3, radius
     if len(pairs) >= min_matched and scale / (1.02 * ratio) <= fitted <= scale * 1.02 * ratio and len(pairs) >= best['n_seed']:
         out['status'] = SOLVE_NOMINAL
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F22: ApEmpiricalPsf - the effective PSF of the stars, PSF-fitting photometry, star removal (csrc/epsf.hip, DESIGN 4.3n;
+# photutils absent, parity unpinned; the definition is restated in tests/epsf_model.py)
+EPSF_SMOOTHING = {'quartic': 4, 'quadratic': 2, 'none': None}
+EPSF_REC_COLUMNS = ('flux_fit', 'x_fit', 'y_fit', 'sky_fit', 'chi2', 'npix', 'niter', 'fit_ok')
+
+
+def epsf_grid_size(o, R):
+    """G = 2 o R + 1 for oversampling o in 1 .. 4 and stamp radius R in 2 .. 32 pixels (ValueError otherwise)."""
+    if isinstance(o, bool) or isinstance(R, bool) or int(o) != o or int(R) != R:
+        raise ValueError('oversampling and radius must be integers, got %r and %r' % (o, R))
+    o, R = int(o), int(R)
+    if not 1 <= o <= _lib.EPSF_MAX_OVERSAMPLING:
+        raise ValueError('oversampling = %d is outside 1 .. %d' % (o, _lib.EPSF_MAX_OVERSAMPLING))
+    if not 2 <= R <= _lib.EPSF_MAX_RADIUS:
+        raise ValueError('radius = %d is outside 2 .. %d' % (R, _lib.EPSF_MAX_RADIUS))
+    return 2 * o * R + 1
+
+
+def _epsf_grid(E, o):
+    """(E, o, R) of a grid argument: a square float32 device tensor [G, G] with G = 2 o R + 1."""
+    if not torch.is_tensor(E) or E.dtype != torch.float32 or E.dim() != 2 or E.shape[0] != E.shape[1]:
+        raise ValueError('the ePSF grid must be a square float32 tensor, got %s' % (
+            '%s %s' % (E.dtype, tuple(E.shape)) if torch.is_tensor(E) else type(E).__name__))
+    _need_cuda(E)
+    if isinstance(o, bool) or int(o) != o or int(o) < 1:
+        raise ValueError('oversampling = %r is not a positive integer' % (o,))
+    G, o = int(E.shape[0]), int(o)
+    if (G - 1) % (2 * o):
+        raise ValueError('a grid of %d nodes per axis is not 2 o R + 1 for oversampling %d' % (G, o))
+    R = (G - 1) // (2 * o)
+    epsf_grid_size(o, R)
+    return E.contiguous(), o, R
+
+
+def _epsf_rows(a, cols, name, device):
+    """A star table argument: [n, cols] float64 on the device (a NumPy array, a sequence or a tensor)."""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, cols)))
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError('%s must have the shape [n, %d], got %s' % (name, cols, tuple(t.shape)))
+    if t.shape[0] >= 2 ** 31:
+        raise ValueError('%s has too many rows' % name)
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def epsf_smoothing_taps(kind='quartic'):
+    """The 5 x 5 smoothing taps (float64 [5, 5], row-major) of the update: the weights with which the least-squares fit of the
+    full bivariate polynomial of degree 4 ('quartic') or 2 ('quadratic') to a 5 x 5 neighbourhood gives its value at the centre
+    - the centre row of the fit's pseudo-inverse, computed here with numpy.linalg.  'none': the identity."""
+    if kind not in EPSF_SMOOTHING:
+        raise ValueError('smoothing = %r; allowed: %s' % (kind, list(EPSF_SMOOTHING)))
+    deg = EPSF_SMOOTHING[kind]
+    taps = np.zeros((5, 5))
+    if deg is None:
+        taps[2, 2] = 1.0
+        return taps
+    yy, xx = np.mgrid[-2:3, -2:3].astype(np.float64)
+    terms = [(a, b) for a in range(deg + 1) for b in range(deg + 1 - a)]                 # x^a y^b, a + b <= deg; (0, 0) first
+    A = np.stack([xx.ravel() ** a * yy.ravel() ** b for a, b in terms], axis=1)           # [25, terms]
+    return np.linalg.pinv(A)[0].reshape(5, 5)                                            # the constant term = the value at (0, 0)
+
+
+def epsf_accumulate(image, stars, E, o, sigma=2.5, maxiters=5):
+    """The sigma-clipped mean residual of the stars' pixels about the ePSF E at every node (apgpu_epsf_accumulate_f32).  stars:
+    [n, 4] = flux, x, y, sky.  Returns (mean float64 [G, G], count int32 [G, G]) on the device."""
+    image = _image_f32(image, 'image')
+    E, o, R = _epsf_grid(E, o)
+    stars = _epsf_rows(stars, 4, 'stars', image.device)
+    if not float(sigma) > 0 or int(maxiters) < 0:
+        raise ValueError('sigma (%r) must be > 0 and maxiters (%r) >= 0' % (sigma, maxiters))
+    G = int(E.shape[0])
+    mean = torch.empty((G, G), dtype=torch.float64, device=image.device)
+    count = torch.empty((G, G), dtype=torch.int32, device=image.device)
+    check(_lib.load().apgpu_epsf_accumulate_f32(_ptr(image), int(image.shape[0]), int(image.shape[1]), _ptr(stars), int(stars.shape[0]),
+                                                _ptr(E), o, R, float(sigma), int(maxiters), _ptr(mean), _ptr(count), _stream()))
+    return mean, count
+
+
+def epsf_shift(E, o, dx, dy, scale=1.0):
+    """The grid of E(u + (dx, dy)) scale at its own nodes u (apgpu_epsf_shift_f32): a new float32 device tensor."""
+    E, o, R = _epsf_grid(E, o)
+    if not all(math.isfinite(float(v)) for v in (dx, dy, scale)):
+        raise ValueError('the offset (%r, %r) and the scale %r must be finite' % (dx, dy, scale))
+    out = torch.empty(tuple(E.shape), dtype=torch.float32, device=E.device)
+    check(_lib.load().apgpu_epsf_shift_f32(_ptr(E), o, R, float(dx), float(dy), float(scale), _ptr(out), _stream()))
+    return out
+
+
+def epsf_centroid(E, o, r_fit=None):
+    """(dx, dy) pixels: the centre of mass of max(E, 0) over the nodes within r_fit of the centre (None: all), in float64 on the
+    host from a NumPy copy of the grid.  (0, 0) for a grid without positive weight."""
+    E = np.asarray(E, np.float64)
+    G = E.shape[0]
+    half = (G - 1) // 2
+    off = (np.arange(G) - half) / float(o)
+    w = np.maximum(E, 0.0)
+    if r_fit is not None:
+        w = np.where(off[:, None] ** 2 + off[None, :] ** 2 <= float(r_fit) ** 2, w, 0.0)
+    tot = w.sum()
+    if not (tot > 0 and np.isfinite(tot)):
+        return 0.0, 0.0
+    return float((w.sum(axis=0) * off).sum() / tot), float((w.sum(axis=1) * off).sum() / tot)
+
+
+def epsf_update(E, mean, count, o, taps='quartic', min_count=1, r_fit=None, recentre=True, normalise=True):
+    """One update of the ePSF: E + mean where count >= min_count, the 5 x 5 smoothing with `taps` (a name of
+    epsf_smoothing_taps or 25 numbers) - one kernel (apgpu_epsf_update_f32) -, then the recentring by the centre of mass
+    (epsf_centroid; a shift of at least 1e-6 px goes through epsf_shift) and the normalisation sum(E) / o^2 = 1.
+    Returns (the new grid, (dx, dy) of the recentring)."""
+    E, o, R = _epsf_grid(E, o)
+    G = int(E.shape[0])
+    _need_cuda(mean, count)
+    if mean.dtype != torch.float64 or count.dtype != torch.int32 or tuple(mean.shape) != (G, G) or tuple(count.shape) != (G, G):
+        raise ValueError('mean (float64) and count (int32) must have the grid\'s shape %s' % ((G, G),))
+    taps = np.ascontiguousarray(epsf_smoothing_taps(taps) if isinstance(taps, str) else np.asarray(taps, np.float64))
+    if taps.size != 25 or not np.all(np.isfinite(taps)):
+        raise ValueError('taps must be 25 finite numbers')
+    out = torch.empty((G, G), dtype=torch.float32, device=E.device)
+    check(_lib.load().apgpu_epsf_update_f32(_ptr(E), _ptr(mean.contiguous()), _ptr(count.contiguous()), o, R, int(min_count),
+                                            taps.ctypes.data_as(C.POINTER(C.c_double)), _ptr(out), _stream()))
+    delta = (0.0, 0.0)
+    if recentre:
+        delta = epsf_centroid(out.cpu().numpy(), o, r_fit)
+        if math.hypot(*delta) >= 1e-6:
+            out = epsf_shift(out, o, delta[0], delta[1])
+    if normalise:
+        tot = float(out.cpu().numpy().astype(np.float64).sum()) / (o * o)
+        if tot > 0 and math.isfinite(tot):
+            out = epsf_shift(out, o, 0.0, 0.0, 1.0 / tot)
+    return out, delta
+
+
+def epsf_fit(image, init, E, o, r_fit, fit_sky=False, gain=0.0, readnoise=0.0, max_iter=50, prev=None):
+    """PSF-fitting photometry (apgpu_epsf_fit_f32): flux and centre, and the sky with fit_sky, of every star of init ([n, 4] =
+    flux, x, y, sky) from the pixels within r_fit of its rounded centre.  gain > 0: weights 1 / (readnoise^2 + max(model, 0) /
+    gain), else uniform.  prev ([n, 3] = f0, x0, y0): `image` is a residual image and each star's own previous model is added back.
+    Returns the records, float64 [n, 8] on the device: EPSF_REC_COLUMNS."""
+    image = _image_f32(image, 'image')
+    E, o, R = _epsf_grid(E, o)
+    init = _epsf_rows(init, 4, 'init', image.device)
+    n = int(init.shape[0])
+    if prev is not None:
+        prev = _epsf_rows(prev, 3, 'prev', image.device)
+        if int(prev.shape[0]) != n:
+            raise ValueError('prev has %d rows for %d stars' % (prev.shape[0], n))
+    if not 1.0 <= float(r_fit) <= _lib.EPSF_MAX_RADIUS:
+        raise ValueError('r_fit = %r is outside 1 .. %d' % (r_fit, _lib.EPSF_MAX_RADIUS))
+    if not float(gain) >= 0 or not float(readnoise) >= 0 or int(max_iter) < 1:
+        raise ValueError('gain (%r) and readnoise (%r) must be >= 0 and max_iter (%r) >= 1' % (gain, readnoise, max_iter))
+    rec = torch.empty((n, _lib.EPSF_REC), dtype=torch.float64, device=image.device)
+    check(_lib.load().apgpu_epsf_fit_f32(_ptr(image), int(image.shape[0]), int(image.shape[1]), _ptr(init), _ptr(prev), n, _ptr(E), o, R,
+                                         float(r_fit), int(bool(fit_sky)), float(gain), float(readnoise), int(max_iter), _ptr(rec),
+                                         _stream()))
+    return rec
+
+
+def epsf_tile_lists(x, y, R, shape, device='cuda'):
+    """The stars of every 32 x 32-pixel tile of an image of `shape` in CSR form: (offsets int32 [tiles + 1], stars int32 [entries]),
+    tiles row-major, ascending star index within a tile.  A star is listed in the tiles its stamp's bounding box
+    [x - R, x + R] x [y - R, y + R] touches; one with a non-finite centre in none.  Built on the host."""
+    H, W = _image_shape(shape)
+    T = _lib.EPSF_TILE
+    ty, tx = -(-H // T), -(-W // T)
+    x, y = np.asarray(x, np.float64).reshape(-1), np.asarray(y, np.float64).reshape(-1)
+    if x.shape != y.shape:
+        raise ValueError('x and y must have one length, got %d and %d' % (x.size, y.size))
+    R = float(R)
+    tiles, stars = [], []
+    ok = np.isfinite(x) & np.isfinite(y) & (x + R >= 0) & (x - R <= W - 1) & (y + R >= 0) & (y - R <= H - 1)
+    for s in np.flatnonzero(ok):
+        x0, x1 = max(int(math.ceil(x[s] - R)), 0) // T, min(int(math.floor(x[s] + R)), W - 1) // T
+        y0, y1 = max(int(math.ceil(y[s] - R)), 0) // T, min(int(math.floor(y[s] + R)), H - 1) // T
+        for b in range(y0, y1 + 1):
+            for a in range(x0, x1 + 1):
+                tiles.append(b * tx + a)
+                stars.append(s)
+    tiles, stars = np.asarray(tiles, np.int64), np.asarray(stars, np.int64)
+    if tiles.size >= 2 ** 31:
+        raise ValueError('too many tile entries')
+    order = np.argsort(tiles, kind='stable')
+    offsets = np.zeros(ty * tx + 1, np.int64)
+    np.cumsum(np.bincount(tiles, minlength=ty * tx), out=offsets[1:])
+    return (torch.from_numpy(offsets.astype(np.int32)).to(device), torch.from_numpy(stars[order].astype(np.int32)).to(device))
+
+
+def epsf_render(image, stars, E, o, lists=None, shape=None, model=True, residual=True):
+    """The image of the stars ([n, 3] = flux, x, y) under the ePSF and / or image minus it (apgpu_epsf_render_f32): (model, residual)
+    float32 device planes, None for the one not asked for.  image may be None with shape = (H, W) when only the model is
+    wanted.  lists: epsf_tile_lists of these stars (built here when None).  NaN pixels stay NaN in the residual."""
+    E, o, R = _epsf_grid(E, o)
+    if image is None:
+        if residual or shape is None:
+            raise ValueError('without an image only the model can be rendered, and shape is needed')
+        H, W = _image_shape(shape)
+    else:
+        image = _image_f32(image, 'image')
+        H, W = int(image.shape[0]), int(image.shape[1])
+    if not (model or residual):
+        raise ValueError('neither the model nor the residual is asked for')
+    stars = _epsf_rows(stars, 3, 'stars', E.device)
+    n = int(stars.shape[0])
+    if lists is None:
+        sh = stars.cpu().numpy()
+        lists = epsf_tile_lists(sh[:, 1], sh[:, 2], R, (H, W), E.device)
+    offsets, idx = lists
+    _need_cuda(offsets, idx)
+    n_tiles = -(-H // _lib.EPSF_TILE) * -(-W // _lib.EPSF_TILE)
+    if offsets.dtype != torch.int32 or idx.dtype != torch.int32 or offsets.numel() != n_tiles + 1 or offsets.dim() != 1 or idx.dim() != 1:
+        raise ValueError('lists must be (offsets int32 [%d], stars int32 [entries]) of epsf_tile_lists for this shape' % (n_tiles + 1))
+    offsets, idx = offsets.contiguous(), idx.contiguous()
+    m = torch.empty((H, W), dtype=torch.float32, device=E.device) if model else None
+    r = torch.empty((H, W), dtype=torch.float32, device=E.device) if residual else None
+    check(_lib.load().apgpu_epsf_render_f32(_ptr(image), H, W, _ptr(stars) if n else None, n, _ptr(offsets), _ptr(idx) if idx.numel() else None,
+                                            int(idx.numel()), _ptr(E), o, R, _ptr(m), _ptr(r), _stream()))
+    return m, r
+
+
+def epsf_select_stars(x, y, flux, shape, R, r_fit, psbl_sat=None, max_stars=500):
+    """The indices of the stars an ePSF is built from, brightest first: not flagged in psbl_sat, finite x, y and flux > 0, at least
+    R + 2 pixels from every edge, no other star of the whole list (flagged ones too) within R + r_fit, the max_stars brightest."""
+    H, W = _image_shape(shape)
+    x, y, flux = (np.asarray(v, np.float64).reshape(-1) for v in (x, y, flux))
+    n = x.size
+    sat = np.zeros(n, bool) if psbl_sat is None else np.asarray(psbl_sat).astype(bool).reshape(-1)
+    pos = np.isfinite(x) & np.isfinite(y)
+    with np.errstate(invalid='ignore'):
+        ok = pos & ~sat & np.isfinite(flux) & (flux > 0) & (x >= R + 2) & (x <= W - 1 - (R + 2)) & (y >= R + 2) & (y <= H - 1 - (R + 2))
+    cand, others = np.flatnonzero(ok), np.flatnonzero(pos)
+    lim2 = float(R + r_fit) ** 2
+    keep = []
+    for s in cand:
+        d2 = (x[others] - x[s]) ** 2 + (y[others] - y[s]) ** 2
+        if np.count_nonzero(d2 < lim2) <= 1:                                     # itself
+            keep.append(s)
+    keep = np.asarray(keep, np.int64)
+    order = np.argsort(-flux[keep], kind='stable')
+    return keep[order][:int(max_stars)]
+
+
+def epsf_build(image, x, y, flux, sky, o=4, R=12, r_fit=None, psbl_sat=None, max_stars=500, n_iter=8, tol=1e-4, sigma=2.5, maxiters=5,
+               smoothing='quartic', min_count=1, fit_sky=False, gain=0.0, readnoise=0.0, max_iter=50, min_stars=1):
+    """The empirical PSF of an image from a star list (x, y: centres, x = column; flux: the aperture sums; sky: per pixel): from
+    E = 0, rounds of epsf_accumulate -> epsf_update -> epsf_fit over the stars of epsf_select_stars, until the grid changes by at
+    most tol max(E) or n_iter rounds are done (none with fewer than min_stars stars).  r_fit: None = 2.  Returns dict(epsf: float32 device grid [G, G]; o, R, r_fit;
+    index: the chosen stars' rows in the list; stars: their fitted records, float64 NumPy [n, 8] (EPSF_REC_COLUMNS); change: the
+    relative change of every round; count: the last round's int32 NumPy counts [G, G]; niter)."""
+    image = _image_f32(image, 'image')
+    G = epsf_grid_size(o, R)
+    o, R = int(o), int(R)
+    r_fit = 2.0 if r_fit is None else float(r_fit)
+    x, y, flux = (np.asarray(v, np.float64).reshape(-1) for v in (x, y, flux))
+    sky = np.broadcast_to(np.asarray(sky, np.float64).reshape(-1), x.shape) if x.size else np.zeros(0)
+    if not (x.shape == y.shape == flux.shape):
+        raise ValueError('x, y and flux must have one length')
+    index = epsf_select_stars(x, y, flux, image.shape, R, r_fit, psbl_sat, max_stars)
+    cur = np.stack([flux[index], x[index], y[index], sky[index]], axis=1) if index.size else np.zeros((0, 4))
+    taps = epsf_smoothing_taps(smoothing)
+    E = torch.zeros((G, G), dtype=torch.float32, device=image.device)
+    rec = np.zeros((0, _lib.EPSF_REC))
+    change, count, done = [], np.zeros((G, G), np.int32), 0
+    for _ in range(int(n_iter) if index.size >= max(int(min_stars), 1) else 0):
+        mean, cnt = epsf_accumulate(image, cur, E, o, sigma, maxiters)
+        E_new, _delta = epsf_update(E, mean, cnt, o, taps, min_count, r_fit)
+        new_h, old_h = E_new.cpu().numpy().astype(np.float64), E.cpu().numpy().astype(np.float64)
+        peak = float(new_h.max())
+        change.append(float(np.abs(new_h - old_h).max()) / peak if peak > 0 else float('inf'))
+        E, count, done = E_new, cnt.cpu().numpy(), done + 1
+        rec = epsf_fit(image, cur, E, o, r_fit, fit_sky, gain, readnoise, max_iter).cpu().numpy()
+        cur = rec[:, :4].copy()                                                     # (a star whose fit failed kept its values)
+        if change[-1] <= tol:
+            break
+    return dict(epsf=E, o=o, R=R, r_fit=r_fit, index=index, stars=rec, change=change, count=count, niter=done)
+
+
+def epsf_stamp(E, o):
+    """The ePSF at integer pixel offsets: every o-th node of the grid, [2R + 1, 2R + 1], negative values set to 0, normalised to
+    sum 1 in float64, as float32 NumPy - what ApDeconvolve.normalise_stamp accepts."""
+    E = np.asarray(E.cpu() if torch.is_tensor(E) else E, np.float64)
+    if E.ndim != 2 or E.shape[0] != E.shape[1] or isinstance(o, bool) or int(o) != o or int(o) < 1 or (E.shape[0] - 1) % (2 * int(o)):
+        raise ValueError('a grid of shape %s is not [2 o R + 1] squared for oversampling %r' % (E.shape, o))
+    epsf_grid_size(int(o), (E.shape[0] - 1) // (2 * int(o)))
+    p = np.maximum(E[::int(o), ::int(o)], 0.0)
+    tot = p.sum()
+    if not (np.all(np.isfinite(p)) and tot > 0):
+        raise ValueError('the ePSF has no positive finite weight at the pixel offsets')
+    return (p / tot).astype(np.float32)

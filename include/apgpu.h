@@ -1177,6 +1177,61 @@ int apgpu_sky_project(const double *ra, const double *dec, int64_t n, double ra0
 int apgpu_cell_select(const double *x, const double *y, int64_t n, const double *cells, int64_t n_cells, int32_t capacity, int32_t *idx,
                       int32_t *count, int32_t *inside, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F22 Empirical PSF, PSF-fitting photometry and star removal.  The reference has no such stage (photutils is absent);
+ *     this is the project's own definition after Anderson & King (2000), restated in tests/epsf_model.py (PARITY UNPINNED).
+ *     All arithmetic float64, every operation rounds on its own.
+ *
+ *     The grid E: device float32 [G][G], G = 2 o R + 1, o = oversampling in 1 .. APGPU_EPSF_MAX_OVERSAMPLING, R = radius in
+ *       2 .. APGPU_EPSF_MAX_RADIUS; node (j, i) is the offset ((i - oR) / o, (j - oR) / o) pixels (x = column) from a star's centre.
+ *       E(dx, dy) is the separable Keys cubic convolution (a = -0.5) of the grid at u = dx o + oR, v = dy o + oR: with iu = floor(u),
+ *       t = u - iu the nodes iu - 1 .. iu + 2 (clamped to 0 .. G - 1) carry the weights w0 .. w3 of apgpu_surface_apply_f32, a row
+ *       is ((w0 e0 + w1 e1) + w2 e2) + w3 e3 and the value the same expression of the row weights and the four rows.  It is 0 where
+ *       |dx| <= R and |dy| <= R do not both hold.  (csrc/epsf_core.h)
+ *     apgpu_epsf_accumulate_f32: stars = device float64 [n][4] (flux f, x, y, sky).  A star takes part if 0 < f < inf, sky is finite
+ *       and |x|, |y| <= 1e9.  Pixel p of an axis belongs to node k = floor((p - x) o + 0.5) + oR (at most one pixel per node, axis
+ *       and star); the sample of star s at node (j, i) is r = (d - sky) / f - E(px - x, py - y) for that pixel if it lies in the
+ *       image and d and r are finite.  Per node: bounds (-inf, inf); a round counts and sums the r inside the closed bounds, ends
+ *       the clip if the count is that of the round before, else takes mean = sum / count, std = sqrt(sum (r - mean)^2 / count) and
+ *       the new bounds mean -+ sigma std; at most maxiters rounds clip.  mean_out [G][G] float64 (0 where count is 0), count_out
+ *       [G][G] int32.  One wavefront per node, lanes stride the stars, butterfly sums: the same bytes on every run.
+ *     apgpu_epsf_update_f32: out (j, i) = float32(sum_a sum_b taps[a][b] T(clamp(j + a - 2), clamp(i + b - 2))) in row-major order of
+ *       (a, b), T = double(E) + mean where count >= min_count, else double(E).  taps: HOST float64 [5][5].  out must not be grid.
+ *     apgpu_epsf_shift_f32: out (j, i) = float32(E((i - oR) / o + dx, (j - oR) / o + dy) scale).  out must not be grid.
+ *     apgpu_epsf_fit_f32: init = device float64 [n][4] (f, x, y, sky); damped Gauss-Newton for (f, x, y), and sky with fit_sky, of
+ *       f E(px - x, py - y) + sky to the pixels with (px - cx)^2 + (py - cy)^2 <= r_fit^2 about (cx, cy) = rint of the initial
+ *       centre, inside the image, with a finite datum.  The datum is the pixel, or with prev (device float64 [n][3] = f0, x0, y0; may
+ *       be NULL) pixel + f0 E(px - x0, py - y0): `image` is then a residual image.  Weights 1, or with gain > 0
+ *       1 / (readnoise^2 + max(model, 0) / gain), the model being that of the point a step starts from.  It stops when a step has |dx|, |dy| < 1e-7 and |df| <= 1e-9 |f|, or after max_iter
+ *       iterations.  rec_out: float64 [n][APGPU_EPSF_REC] = f, x, y, sky, chi^2, pixels used, iterations, ok; a star with fewer than
+ *       6 usable pixels, a non-finite input, a system that is not positive definite or a non-finite result has ok = 0, chi^2 = NaN
+ *       and its input values.  One wavefront per star.
+ *     apgpu_epsf_render_f32: stars = device float64 [n][3] (f, x, y); tile_offsets int32 [tiles + 1], tile_stars int32 [n_entries]: the
+ *       stars of every APGPU_EPSF_TILE-pixel square tile (row-major tiles, ceil(width / TILE) per row) in CSR form.  Per pixel the
+ *       sum of f E(px - x, py - y) over its tile's list in list order (entries outside 0 .. n - 1 and stars with a non-finite flux
+ *       are skipped); model_out = float32(sum), residual_out = float32(double(image) - sum); either may be NULL, image too if
+ *       residual_out is.  model_out and residual_out must be planes of their own (neither the other nor image).
+ *     APGPU_EINVAL: NULL or misaligned pointers, oversampling, radius or r_fit (1 .. APGPU_EPSF_MAX_RADIUS) out of range, negative
+ *       counts, sigma <= 0, maxiters < 0, max_iter < 1, a non-finite tap, offset or scale, a negative gain or read noise.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_EPSF_MAX_OVERSAMPLING 4
+#define APGPU_EPSF_MAX_RADIUS 32
+#define APGPU_EPSF_REC 8
+#define APGPU_EPSF_TILE 32
+int apgpu_epsf_accumulate_f32(const float *image, int64_t height, int64_t width, const double *stars, int32_t n_stars,
+                              const float *grid, int32_t oversampling, int32_t radius, double sigma, int32_t maxiters,
+                              double *mean_out, int32_t *count_out, void *stream);
+int apgpu_epsf_update_f32(const float *grid, const double *mean, const int32_t *count, int32_t oversampling, int32_t radius,
+                          int32_t min_count, const double *taps, float *out, void *stream);
+int apgpu_epsf_shift_f32(const float *grid, int32_t oversampling, int32_t radius, double dx, double dy, double scale, float *out,
+                         void *stream);
+int apgpu_epsf_fit_f32(const float *image, int64_t height, int64_t width, const double *init, const double *prev, int32_t n_stars,
+                       const float *grid, int32_t oversampling, int32_t radius, double r_fit, int32_t fit_sky, double gain,
+                       double readnoise, int32_t max_iter, double *rec_out, void *stream);
+int apgpu_epsf_render_f32(const float *image, int64_t height, int64_t width, const double *stars, int32_t n_stars,
+                          const int32_t *tile_offsets, const int32_t *tile_stars, int32_t n_entries, const float *grid,
+                          int32_t oversampling, int32_t radius, float *model_out, float *residual_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
