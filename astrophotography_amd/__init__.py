@@ -33,6 +33,7 @@ _LAZY = {
     'ApRemoveGradient': ('.core.ApRemoveGradient', 'ApRemoveGradient'),
     'ApAstrometry': ('.core.ApAstrometry', 'ApAstrometry'),
     'ApEmpiricalPsf': ('.core.ApEmpiricalPsf', 'ApEmpiricalPsf'),
+    'ApSubtract': ('.core.ApSubtract', 'ApSubtract'),
 }
 
 __all__ = sorted(_LAZY) + ['__version__']

@@ -38,6 +38,8 @@ GRADIENT_UNITS = [('gradient', 'gradient', [])]
 ASTROMETRY_UNITS = [('astrometry', 'astrometry', [])]
 # ... and the empirical PSF's unit (its interpolant: epsf_core.h)
 EPSF_UNITS = [('epsf', 'epsf', [])]
+# ... and the optimal image subtraction's unit (its basis and spatial polynomials: subtract_core.h)
+SUBTRACT_UNITS = [('subtract', 'subtract', [])]
 
 # -ffp-contract=off: the reference's NumPy expressions round after every operation, so no FMA
 # contraction anywhere; fused operations are written explicitly (fma()) where wanted.
@@ -63,7 +65,7 @@ def compile_units(obj_dir=OBJ):
     units += [('stack_inst_%s_%s_%s' % (tag, ctag, g), 'stack_inst',
                STACK_TU_FLAGS + ['-DAPGPU_INST_RAW=' + raw, '-DAPGPU_INST_CALIB=' + calib, '-DAPGPU_INST_GROUP=' + g])
               for g in STACK_GROUPS for tag, raw in STACK_DTYPES for ctag, calib in STACK_CALIB]
-    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS + GRADIENT_UNITS + ASTROMETRY_UNITS + EPSF_UNITS
+    units += [(u, u, []) for u in LATE_UNITS] + ESD_UNITS + DISTORTION_UNITS + GRADIENT_UNITS + ASTROMETRY_UNITS + EPSF_UNITS + SUBTRACT_UNITS
     for name, src, flags in units:
         stem = os.path.join(obj_dir, name)
         srcp = os.path.join(CSRC, src + '.hip')

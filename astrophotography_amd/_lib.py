@@ -43,6 +43,8 @@ SURFACE_MODEL = {'poly': 0, 'tps': 1}                   # APGPU_SURFACE_POLY, AP
 GRADIENT_MODE = {'subtract': 0, 'divide': 1}            # APGPU_GRADIENT_SUBTRACT, APGPU_GRADIENT_DIVIDE
 CELL_MAX_CAPACITY = 65536                               # APGPU_CELL_MAX_CAPACITY
 EPSF_MAX_OVERSAMPLING, EPSF_MAX_RADIUS, EPSF_REC, EPSF_TILE = 4, 32, 8, 32      # APGPU_EPSF_MAX_OVERSAMPLING, _MAX_RADIUS, _REC, _TILE
+SUBTRACT_MAX_RADIUS, SUBTRACT_MAX_BASIS, SUBTRACT_MAX_DEGREE, SUBTRACT_MAX_HALF = 15, 64, 3, 15     # APGPU_SUBTRACT_MAX_RADIUS, _MAX_BASIS, _MAX_DEGREE, _MAX_HALF
+SUBTRACT_TILE_H, SUBTRACT_TILE_W, SUBTRACT_CONVOLVED_IMAGE = 32, 64, 1                             # APGPU_SUBTRACT_TILE_H, _TILE_W, _CONVOLVED_IMAGE
 
 
 class ApGpuError(RuntimeError):
@@ -229,6 +231,15 @@ SIGNATURES = {
                                      C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
     'apgpu_epsf_render_f32': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_subtract_basis_f64': (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'apgpu_subtract_stamps_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    'apgpu_subtract_apply_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

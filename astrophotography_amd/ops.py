@@ -4163,3 +4163,295 @@ def epsf_stamp(E, o):
     if not (np.all(np.isfinite(p)) and tot > 0):
         raise ValueError('the ePSF has no positive finite weight at the pixel offsets')
     return (p / tot).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# F23: ApSubtract - optimal image subtraction with a spatially varying kernel (csrc/subtract.hip; Alard & Lupton
+# 1998, Alard 2000; the reference has no such stage, parity unpinned; the definition is restated in tests/subtract_model.py)
+SUBTRACT_SIGMAS, SUBTRACT_DEGREES, SUBTRACT_RADIUS = (0.7, 1.5, 3.0), (6, 4, 2), 10
+SUBTRACT_STATUS = {1: 'the footprint leaves the image', 2: 'non-finite template pixel', 4: 'non-finite image pixel', 8: 'masked pixel'}
+
+
+class SubtractNoFit(ArithmeticError):
+    """Fewer usable stamps than the spatial terms need, or normal equations that cannot be solved."""
+
+
+def _poly_count(d):
+    return (d + 1) * (d + 2) // 2
+
+
+def _sub_degree(d, name):
+    if isinstance(d, bool) or int(d) != d or not 0 <= int(d) <= _lib.SUBTRACT_MAX_DEGREE:
+        raise ValueError('%s = %r is outside 0 .. %d' % (name, d, _lib.SUBTRACT_MAX_DEGREE))
+    return int(d)
+
+
+def _sub_ipow(x, k):
+    p = np.ones_like(np.asarray(x, np.float64))
+    for _ in range(k):
+        p = p * x
+    return p
+
+
+def subtract_poly_terms(degree, X, Y):
+    """[terms, ...] float64: X^i Y^j for i + j <= degree, i then j ascending, the powers by repeated multiplication."""
+    return np.stack([_sub_ipow(X, i) * _sub_ipow(Y, j) for i in range(degree + 1) for j in range(degree + 1 - i)])
+
+
+def subtract_norm_coord(p, n):
+    """(2 p - (n - 1)) / max(n - 1, 1): -1 .. 1 over an axis of n pixels."""
+    return (2 * np.asarray(p, np.int64) - (n - 1)) / float(max(n - 1, 1))
+
+
+def kernel_basis(sigmas=SUBTRACT_SIGMAS, degrees=SUBTRACT_DEGREES, radius=SUBTRACT_RADIUS):
+    """The kernel basis of Gaussians times polynomials (apgpu_subtract_basis_f64; host only): a dict of the separable form - filters
+    float64 [NF, 2 r + 1], row, col, even int32 [Nb], scale float64 [Nb] - the dense functions B float64 [Nb, 2 r + 1, 2 r + 1] (B_n(u, v)
+    at [n, v + r, u + r]; every function but the first sums to 0, the first to 1), radius, nb, sigmas and degrees."""
+    sig = np.ascontiguousarray(np.asarray(sigmas, np.float64).ravel())
+    deg = np.asarray(degrees).ravel()
+    if sig.size == 0 or sig.size != deg.size or np.any(deg != deg.astype(np.int64)):
+        raise ValueError('sigmas %r and degrees %r must be as many numbers, the degrees integers' % (sigmas, degrees))
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= _lib.SUBTRACT_MAX_RADIUS:
+        raise ValueError('radius = %r is outside 1 .. %d' % (radius, _lib.SUBTRACT_MAX_RADIUS))
+    if not np.all(np.isfinite(sig) & (sig > 0)) or np.any(deg < 0):
+        raise ValueError('sigmas must be > 0 and degrees >= 0, got %r and %r' % (sigmas, degrees))
+    if sum(_poly_count(int(d)) for d in deg) > _lib.SUBTRACT_MAX_BASIS:
+        raise ValueError('the degrees %r make more than %d basis functions' % (list(deg), _lib.SUBTRACT_MAX_BASIS))
+    deg = np.ascontiguousarray(deg.astype(np.int32))
+    r, M = int(radius), _lib.SUBTRACT_MAX_BASIS
+    kw = 2 * r + 1
+    filters = np.zeros((M, kw), np.float64)
+    row, col, even = (np.zeros(M, np.int32) for _ in range(3))
+    scale = np.zeros(M, np.float64)
+    nf, nb = C.c_int32(0), C.c_int32(0)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    check(_lib.load().apgpu_subtract_basis_f64(sig.ctypes.data_as(dp), deg.ctypes.data_as(ip), int(sig.size), r, filters.ctypes.data_as(dp),
+                                               row.ctypes.data_as(ip), col.ctypes.data_as(ip), scale.ctypes.data_as(dp),
+                                               even.ctypes.data_as(ip), C.byref(nf), C.byref(nb)))
+    nf, nb = nf.value, nb.value
+    filters, row, col, even, scale = filters[:nf].copy(), row[:nb].copy(), col[:nb].copy(), even[:nb].copy(), scale[:nb].copy()
+    B = np.empty((nb, kw, kw))
+    for n in range(nb):
+        B[n] = scale[n] * (filters[col[n]][:, None] * filters[row[n]][None, :])
+        if n > 0 and even[n]:
+            B[n] = B[n] - B[0]
+    return dict(filters=filters, row=row, col=col, even=even, scale=scale, B=B, radius=r, nb=nb, sigmas=[float(s) for s in sig],
+                degrees=[int(d) for d in deg])
+
+
+def _sub_centers(centers, device):
+    c = centers.cpu().numpy() if torch.is_tensor(centers) else np.asarray(centers)
+    c = c.reshape(-1, 2)
+    if c.size and (np.any(c != np.rint(c)) or np.abs(c).max() >= 2 ** 31):
+        raise ValueError('stamp centres must be integer pixels (x, y)')
+    return torch.from_numpy(np.ascontiguousarray(c.astype(np.int32))).to(device)
+
+
+def subtract_stamps(template, image, centers, half, basis, mask=None, gain=0.0, readnoise=0.0):
+    """The normal equations of every stamp (apgpu_subtract_stamps_f32): `template` is the image that the kernel convolves, `image` the one
+    it is matched to; centers [S, 2] integer (x, y); half the stamp's half-size (1 .. 15); basis a dict of kernel_basis.  mask: non-zero
+    pixels refuse the stamps they fall in.  gain > 0 (then readnoise > 0): weights 1 / (readnoise^2 / gain^2 + max(image, 0) / gain).
+    Returns device tensors (gram float64 [S, Nb + 2, Nb + 2], status int32 [S], count int32 [S]): gram[s, :Nb + 1, :Nb + 1] is the Gram
+    matrix of the stamp's fit vectors T (x) B_0 .., 1, gram[s, :Nb + 1, Nb + 1] their products with the image, gram[s, Nb + 1, Nb + 1]
+    sum w I^2; status is 0 or a sum of SUBTRACT_STATUS' bits (the stamp then has zeros and count 0)."""
+    template = _image_f32(template, 'template')
+    image = _plane_like(image, 'image', template)
+    mask = _mask_u8(mask, template.shape, 'mask must have the image shape %s' % (tuple(template.shape),))
+    if isinstance(half, bool) or int(half) != half or not 1 <= int(half) <= _lib.SUBTRACT_MAX_HALF:
+        raise ValueError('half = %r is outside 1 .. %d' % (half, _lib.SUBTRACT_MAX_HALF))
+    if not float(gain) >= 0 or not float(readnoise) >= 0 or not math.isfinite(float(gain)) or not math.isfinite(float(readnoise)) or \
+            (float(gain) > 0 and not float(readnoise) > 0):
+        raise ValueError('gain (%r) and readnoise (%r) must be finite and >= 0, and a gain needs a read noise above 0' % (gain, readnoise))
+    dev = template.device
+    cen = _sub_centers(centers, dev)
+    S, nb = int(cen.shape[0]), int(basis['nb'])
+    filters = torch.from_numpy(np.ascontiguousarray(basis['filters'], np.float64)).to(dev)
+    row, col, even = (np.ascontiguousarray(basis[k], np.int32) for k in ('row', 'col', 'even'))
+    scale = np.ascontiguousarray(basis['scale'], np.float64)
+    gram = torch.empty((S, nb + 2, nb + 2), dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    count = torch.empty(S, dtype=torch.int32, device=dev)
+    ip = C.POINTER(C.c_int32)
+    check(_lib.load().apgpu_subtract_stamps_f32(_ptr(template), _ptr(image), _ptr(mask), int(template.shape[0]), int(template.shape[1]),
+                                                _ptr(cen), S, int(half), int(basis['radius']), _ptr(filters), int(filters.shape[0]),
+                                                row.ctypes.data_as(ip), col.ctypes.data_as(ip), scale.ctypes.data_as(C.POINTER(C.c_double)),
+                                                even.ctypes.data_as(ip), nb, float(gain), float(readnoise), _ptr(gram), _ptr(status),
+                                                _ptr(count), _stream()))
+    return gram, status, count
+
+
+def _sub_design(nb, kdeg, bdeg, X, Y):
+    """P [unknowns, Nb + 1] of a stamp at the normalised centre (X, Y): the unknowns are a_0, then a_{n,t} (n = 1 .. Nb - 1 outside, t
+    inside), then c_t; column m belongs to the fit vector V_m (V_Nb = 1)."""
+    pk, pb = subtract_poly_terms(kdeg, X, Y), subtract_poly_terms(bdeg, X, Y)
+    ntk = len(pk)
+    P = np.zeros((1 + (nb - 1) * ntk + len(pb), nb + 1))
+    P[0, 0] = 1.0
+    for n in range(1, nb):
+        P[1 + (n - 1) * ntk:1 + n * ntk, n] = pk
+    P[1 + (nb - 1) * ntk:, nb] = pb
+    return P
+
+
+def subtract_fit(gram, status, count, centers, shape, basis, kernel_degree=2, bg_degree=1, k=3.0, rounds=3):
+    """The host side of the fit, float64: the normal equations M = sum_s P_s G_s P_s^T of the kept stamps (the spatial terms taken at the
+    stamps' centres), scaled by their diagonal and solved; every stamp's chi^2 per pixel from its own G_s, g_s and sum w I^2; stamps
+    above median + k 1.4826 MAD dropped and the fit made again, at most `rounds` times.  gram, status, count: what subtract_stamps
+    returned (tensors or arrays).  Returns a dict: a0 (the photometric scale), akt [Nb, ntk] (a_{n,t}; row 0 holds a_0 in column 0), bg
+    [ntb], kernels (the composite kernels A_t, float32 [ntk, 2 r + 1, 2 r + 1]), kept (bool [S]), chi2 [S] (NaN for a refused stamp),
+    cond (of the scaled normal matrix), rounds (fits made), margin (the smallest relative distance of a chi^2 to the last cut).
+    Raises SubtractNoFit when fewer stamps are usable than the spatial terms need."""
+    kdeg, bdeg = _sub_degree(kernel_degree, 'kernel_degree'), _sub_degree(bg_degree, 'bg_degree')
+    gram, status, count = (np.asarray(a.cpu().numpy() if torch.is_tensor(a) else a) for a in (gram, status, count))
+    centers = (centers.cpu().numpy() if torch.is_tensor(centers) else np.asarray(centers)).reshape(-1, 2).astype(np.int64)
+    H, W = int(shape[0]), int(shape[1])
+    nb, S = int(basis['nb']), gram.shape[0]
+    if gram.shape[1:] != (nb + 2, nb + 2) or len(centers) != S or len(status) != S or len(count) != S:
+        raise ValueError('gram %s, status, count and centers do not belong to %d stamps of %d basis functions' % (gram.shape, S, nb))
+    if not float(k) > 0 or int(rounds) < 0:
+        raise ValueError('k (%r) must be > 0 and rounds (%r) >= 0' % (k, rounds))
+    ntk, ntb = _poly_count(kdeg), _poly_count(bdeg)
+    Ps = [_sub_design(nb, kdeg, bdeg, float(subtract_norm_coord(cx, W)), float(subtract_norm_coord(cy, H))) for cx, cy in centers]
+    usable = status == 0
+    kept = usable.copy()
+    chi2 = np.full(S, np.nan)
+    margin, made = float('inf'), 0
+    nun = 1 + (nb - 1) * ntk + ntb
+    while True:
+        if kept.sum() < max(ntk, ntb):
+            raise SubtractNoFit('%d usable stamps for %d spatial terms' % (kept.sum(), max(ntk, ntb)))
+        M, rhs = np.zeros((nun, nun)), np.zeros(nun)
+        for s in np.flatnonzero(kept):
+            M = M + Ps[s] @ gram[s, :nb + 1, :nb + 1] @ Ps[s].T
+            rhs = rhs + Ps[s] @ gram[s, :nb + 1, nb + 1]
+        d = np.sqrt(np.diag(M))
+        if not np.all(d > 0) or not np.all(np.isfinite(M)):
+            raise SubtractNoFit('the normal matrix has an empty or non-finite row')
+        Ms = M / d[:, None] / d[None, :]
+        try:
+            theta = np.linalg.solve(Ms, rhs / d) / d
+        except np.linalg.LinAlgError as exc:
+            raise SubtractNoFit('the normal equations are singular') from exc
+        made += 1
+        for s in np.flatnonzero(usable):
+            q = Ps[s].T @ theta
+            chi2[s] = (gram[s, nb + 1, nb + 1] - 2.0 * (q @ gram[s, :nb + 1, nb + 1]) + q @ gram[s, :nb + 1, :nb + 1] @ q) / count[s]
+        if made > int(rounds):
+            break
+        c = chi2[kept]
+        med = np.median(c)
+        cut = med + float(k) * 1.4826 * np.median(np.abs(c - med))
+        drop = kept & (chi2 > cut)
+        margin = float(np.min(np.abs(c - cut)) / cut)
+        if not drop.any():
+            break
+        kept = kept & ~drop
+    akt = np.zeros((nb, ntk))
+    akt[0, 0] = theta[0]
+    akt[1:] = theta[1:1 + (nb - 1) * ntk].reshape(nb - 1, ntk)
+    kernels = np.zeros((ntk,) + basis['B'].shape[1:])
+    for t in range(ntk):
+        for n in range(nb):
+            kernels[t] = kernels[t] + akt[n, t] * basis['B'][n]
+    return dict(a0=float(theta[0]), akt=akt, bg=theta[1 + (nb - 1) * ntk:].copy(), kernels=kernels.astype(np.float32), kept=kept, chi2=chi2,
+                cond=float(np.linalg.cond(Ms)), rounds=made, margin=margin, kernel_degree=kdeg, bg_degree=bdeg)
+
+
+def subtract_kernel_at(fit, x, y, shape):
+    """The fitted kernel at pixel (x, y) of an image of `shape`: float64 [2 r + 1, 2 r + 1], K(u, v) at [v + r, u + r]."""
+    phi = subtract_poly_terms(fit['kernel_degree'], float(subtract_norm_coord(int(x), int(shape[1]))), float(subtract_norm_coord(int(y), int(shape[0]))))
+    return np.tensordot(phi, fit['kernels'].astype(np.float64), 1)
+
+
+def subtract_apply(convolved, other, kernels, kernel_degree, bg, bg_degree, convolved_image=False, a0=1.0, matched=False):
+    """Applies a fitted kernel (apgpu_subtract_apply_f32).  `convolved` is the image the kernel convolves (the template, or with
+    convolved_image=True the image), `other` the one it is compared with; kernels float32 [ntk, 2 r + 1, 2 r + 1] (subtract_fit's
+    'kernels'), bg the background coefficients.  Returns the difference other - (convolved (x) K + B), or with convolved_image
+    ((convolved (x) K + B) - other) / a0; with matched=True (diff, convolved (x) K + B).  NaN where `other` is not finite or the
+    kernel's footprint meets a non-finite pixel of `convolved` or the image's edge."""
+    convolved = _image_f32(convolved, 'convolved')
+    other = _plane_like(other, 'other', convolved)
+    kdeg, bdeg = _sub_degree(kernel_degree, 'kernel_degree'), _sub_degree(bg_degree, 'bg_degree')
+    kn = np.ascontiguousarray(kernels.cpu().numpy() if torch.is_tensor(kernels) else kernels, np.float32)
+    if kn.ndim != 3 or kn.shape[0] != _poly_count(kdeg) or kn.shape[1] != kn.shape[2] or kn.shape[1] % 2 == 0 or \
+            not 1 <= (kn.shape[1] - 1) // 2 <= _lib.SUBTRACT_MAX_RADIUS:
+        raise ValueError('kernels of shape %s are not [%d, 2 r + 1, 2 r + 1] with r in 1 .. %d' % (kn.shape, _poly_count(kdeg), _lib.SUBTRACT_MAX_RADIUS))
+    bgc = np.ascontiguousarray(np.asarray(bg, np.float64).ravel())
+    if bgc.size != _poly_count(bdeg) or not np.all(np.isfinite(bgc)):
+        raise ValueError('bg must be %d finite coefficients' % _poly_count(bdeg))
+    if convolved_image and (not math.isfinite(float(a0)) or float(np.float32(a0)) == 0.0):
+        raise ValueError('a0 = %r must be finite and not 0' % (a0,))
+    kd = torch.from_numpy(kn).to(convolved.device)
+    diff = torch.empty_like(convolved)
+    mt = torch.empty_like(convolved) if matched else None
+    check(_lib.load().apgpu_subtract_apply_f32(_ptr(convolved), _ptr(other), int(convolved.shape[0]), int(convolved.shape[1]), _ptr(kd),
+                                               (kn.shape[1] - 1) // 2, kdeg, bgc.ctypes.data_as(C.POINTER(C.c_double)), bdeg,
+                                               _lib.SUBTRACT_CONVOLVED_IMAGE if convolved_image else 0, float(a0), _ptr(diff), _ptr(mt),
+                                               _stream()))
+    return (diff, mt) if matched else diff
+
+
+def subtract_select_stamps(x, y, flux, shape, half, radius, peak=None, satlevel=None, nx=4, ny=4, per_region=5):
+    """The stamp centres [S, 2] int64 (x, y) from a star list, on the host: stars with a peak at satlevel are dropped; of two stars
+    closer than 2 half the fainter is dropped; stamps whose footprint half + radius leaves the image are dropped; the brightest
+    per_region of every cell of an nx x ny grid are kept.  In the order of falling flux."""
+    H, W = int(shape[0]), int(shape[1])
+    x, y, flux = (np.asarray(a, np.float64).ravel() for a in (x, y, flux))
+    if not (x.size == y.size == flux.size) or int(nx) < 1 or int(ny) < 1 or int(per_region) < 1:
+        raise ValueError('x, y and flux must be as many numbers; nx, ny and per_region at least 1')
+    ok = np.isfinite(x) & np.isfinite(y) & np.isfinite(flux)
+    if peak is not None and satlevel is not None:
+        ok &= ~(np.asarray(peak, np.float64).ravel() >= float(satlevel))
+    order = [i for i in np.argsort(-np.where(ok, flux, -np.inf), kind='stable') if ok[i]]
+    taken, cells, out = [], {}, []
+    F = int(half) + int(radius)
+    for i in order:
+        if any(math.hypot(x[i] - x[j], y[i] - y[j]) < 2 * half for j in taken):
+            continue
+        taken.append(i)
+        cx, cy = int(np.rint(x[i])), int(np.rint(y[i]))
+        if cx - F < 0 or cx + F >= W or cy - F < 0 or cy + F >= H:
+            continue
+        cell = (min(cx * int(nx) // W, int(nx) - 1), min(cy * int(ny) // H, int(ny) - 1))
+        if cells.get(cell, 0) >= int(per_region):
+            continue
+        cells[cell] = cells.get(cell, 0) + 1
+        out.append((cx, cy))
+    return np.array(out, np.int64).reshape(-1, 2)
+
+
+def optimal_subtract(image, template, stars=None, centers=None, mask=None, sigmas=SUBTRACT_SIGMAS, degrees=SUBTRACT_DEGREES,
+                     radius=SUBTRACT_RADIUS, kernel_degree=2, bg_degree=1, half=15, regions=(4, 4), per_region=5, satlevel=None, gain=0.0,
+                     readnoise=0.0, k=3.0, rounds=3, convolve='template', fwhm=None, matched=False):
+    """Optimal image subtraction end to end: D = image - (template (x) K + B) with the kernel K(u, v; x, y) and the background B(x, y)
+    fitted on stamps around stars.  stars: [n, 3] or [n, 4] = x, y, flux[, peak] (an array or a tensor), from which
+    subtract_select_stamps chooses; or centers [S, 2] as they are.  convolve: 'template', 'image' (D = (image (x) K + B - template) /
+    a0, still on the image's flux scale) or 'auto' (the one with the smaller of fwhm = (image, template)).
+    Returns a dict: diff, matched (with matched=True), centers, status, convolve and the entries of subtract_fit."""
+    image = _image_f32(image, 'image')
+    template = _plane_like(template, 'template', image)
+    if convolve not in ('template', 'image', 'auto'):
+        raise ValueError("convolve = %r; allowed: 'template', 'image', 'auto'" % (convolve,))
+    if convolve == 'auto':
+        if fwhm is None or not all(math.isfinite(float(f)) and float(f) > 0 for f in fwhm):
+            raise ValueError("convolve='auto' needs fwhm = (image, template) in pixels")
+        convolve = 'image' if float(fwhm[0]) < float(fwhm[1]) else 'template'
+    basis = kernel_basis(sigmas, degrees, radius)
+    if centers is None:
+        if stars is None:
+            raise ValueError('give stars (x, y, flux[, peak]) or stamp centers')
+        st = np.asarray(stars.cpu().numpy() if torch.is_tensor(stars) else stars, np.float64)
+        if st.ndim != 2 or st.shape[1] not in (3, 4):
+            raise ValueError('stars must be [n, 3] (x, y, flux) or [n, 4] (x, y, flux, peak), got shape %s' % (st.shape,))
+        centers = subtract_select_stamps(st[:, 0], st[:, 1], st[:, 2], image.shape, half, basis['radius'],
+                                         st[:, 3] if st.shape[1] == 4 else None, satlevel, regions[0], regions[1], per_region)
+    centers = (centers.cpu().numpy() if torch.is_tensor(centers) else np.asarray(centers)).reshape(-1, 2).astype(np.int64)
+    src, oth = (template, image) if convolve == 'template' else (image, template)
+    gram, status, count = subtract_stamps(src, oth, centers, half, basis, mask, gain, readnoise)
+    status = status.cpu().numpy()
+    fit = subtract_fit(gram, status, count, centers, image.shape, basis, kernel_degree, bg_degree, k, rounds)
+    res = subtract_apply(src, oth, fit['kernels'], fit['kernel_degree'], fit['bg'], fit['bg_degree'], convolve == 'image', fit['a0'], matched)
+    out = dict(fit, diff=res[0] if matched else res, centers=centers, status=status, convolve=convolve, basis=basis)
+    if matched:
+        out['matched'] = res[1]
+    return out

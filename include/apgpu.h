@@ -1232,6 +1232,62 @@ int apgpu_epsf_render_f32(const float *image, int64_t height, int64_t width, con
                           const int32_t *tile_offsets, const int32_t *tile_stars, int32_t n_entries, const float *grid,
                           int32_t oversampling, int32_t radius, float *model_out, float *residual_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F23 Optimal image subtraction: the kernel fit of Alard & Lupton (1998) with the spatial variation of Alard (2000).
+ *     The reference has no such stage; this is the project's own definition, restated in tests/subtract_model.py (PARITY UNPINNED).
+ *     Every operation rounds on its own, no contraction.  x = column, y = row; (T (x) K)(x, y) = sum_{u, v} K(u, v) T(x - u, y - v),
+ *     a kernel of radius r is stored [2 r + 1][2 r + 1] with K(u, v) at [v + r][u + r].
+ *
+ *     apgpu_subtract_basis_f64 (host only, no device work): the basis of n_gauss Gaussians (sigmas_host > 0) times polynomials of
+ *       the degrees degrees_host in its separable form (csrc/subtract_core.h).  Functions are ordered g, then i, then j ascending
+ *       (i + j <= degree g); the 1-D filters g, then power p ascending: filters[f][u + r] = exp(-u^2 / (2 sigma_g^2)) u^p (u^p by
+ *       repeated multiplication).  Function n = (g, i, j): b_n(u, v) = filters[row[n]][u + r] filters[col[n]][v + r], row[n] the filter
+ *       of (g, i), col[n] that of (g, j); even[n] = 1 where i and j are both even, and then scale[n] = 1 / sum b_n (over v ascending of
+ *       the sums over u ascending), else 1.  B_n = scale[n] b_n, minus B_0 where even[n] and n > 0: every function but the first sums
+ *       to 0.  The output arrays hold APGPU_SUBTRACT_MAX_BASIS entries (filters: APGPU_SUBTRACT_MAX_BASIS rows of 2 r + 1).
+ *       APGPU_EUNSUPPORTED: radius above APGPU_SUBTRACT_MAX_RADIUS, more than APGPU_SUBTRACT_MAX_BASIS functions.
+ *     apgpu_subtract_stamps_f32: per stamp s of half-size `half` (n = 2 half + 1 pixels a side) about the integer pixel centers[s] =
+ *       (x, y) (device int32 [S][2]), in float64 with every accumulator starting at +0:
+ *         R_f(x, y') = sum_u filters[f][u + r] T(x - u, y'), u ascending;  c_n(x, y) = sum_v filters[col[n]][v + r] R_row[n](x, y - v),
+ *         v ascending;  V_n = scale[n] c_n, minus V_0 where even[n] and n > 0 (= T (x) B_n);  V_Nb = 1;  V_Nb+1 = I;
+ *         gram_out[s][a][b] = gram_out[s][b][a] = sum over the stamp's pixels in row-major order of (w V_a) V_b for a <= b
+ *       (float64 [S][Nb + 2][Nb + 2]: the Gram matrix of the Nb + 1 fit vectors, their products with I, and sum w I^2), w = 1 or, with
+ *       gain > 0 (then readnoise > 0), 1 / (readnoise^2 / gain^2 + max(I, 0) / gain).  filters: DEVICE float64 [n_filters][2 r + 1]; row,
+ *       col, scale, even: HOST arrays of n_basis entries.  status_out[s] (int32): 0, or the bits 1 (the footprint half + r leaves the
+ *       image; the other bits are then not looked for), 2 (a non-finite template pixel in the footprint), 4 (a non-finite image
+ *       pixel in the stamp), 8 (a non-zero mask pixel in the stamp; mask uint8 [H][W], may be NULL); count_out[s] = n^2 or, with a
+ *       status, 0 and a gram of zeros.  One workgroup per stamp, no atomics: the same bytes on every run.
+ *     apgpu_subtract_apply_f32: kernels = device float32 [nt][2 r + 1][2 r + 1], nt = (kernel_degree + 1)(kernel_degree + 2) / 2 composite
+ *       kernels A_t, one per spatial term phi_t = X^i Y^j (i + j <= degree, i then j ascending; X = (2 x - (W - 1)) / max(W - 1, 1),
+ *       Y likewise, powers by repeated multiplication, in float64).  S = `convolved` with non-finite and out-of-image pixels as NaN,
+ *       O = `other`.  In float32: conv_t = sum_u sum_v A_t(u, v) S(x - u, y - v), u ascending outside, v ascending inside, from +0;
+ *       conv = sum_t float32(phi_t) conv_t, t ascending from +0; B = float32(sum_t bg_host[t] phi_t) (float64, t ascending from +0, the
+ *       terms of bg_degree); matched_out (may be NULL) = conv + B; diff_out = (O - conv) - B, or with APGPU_SUBTRACT_CONVOLVED_IMAGE
+ *       ((conv + B) - O) / a0 (`convolved` is then the image, `other` the template; a0 finite, not 0); diff_out = NaN where O is not
+ *       finite (and, by propagation, where a pixel of the footprint of S is NaN); every NaN written is the quiet NaN 0x7fc00000.
+ *       The outputs are planes of their own.
+ *     APGPU_EINVAL: NULL or misaligned pointers, shapes <= 0, a radius or half-size below 1, degrees outside 0 .. 3, filter indices
+ *       out of range, a non-finite scale, coefficient or a0, gain or readnoise negative, unknown flags.
+ * ------------------------------------------------------------------------------------------- */
+#define APGPU_SUBTRACT_MAX_RADIUS 15
+#define APGPU_SUBTRACT_MAX_BASIS 64
+#define APGPU_SUBTRACT_MAX_DEGREE 3
+#define APGPU_SUBTRACT_MAX_HALF 15
+#define APGPU_SUBTRACT_TILE_H 32
+#define APGPU_SUBTRACT_TILE_W 64
+#define APGPU_SUBTRACT_CONVOLVED_IMAGE 1
+int apgpu_subtract_basis_f64(const double *sigmas_host, const int32_t *degrees_host, int32_t n_gauss, int32_t radius, double *filters_host,
+                             int32_t *row_host, int32_t *col_host, double *scale_host, int32_t *even_host, int32_t *n_filters_host,
+                             int32_t *n_basis_host);
+int apgpu_subtract_stamps_f32(const float *tmpl, const float *image, const uint8_t *mask, int64_t height, int64_t width,
+                              const int32_t *centers, int32_t n_stamps, int32_t half, int32_t radius, const double *filters,
+                              int32_t n_filters, const int32_t *row_host, const int32_t *col_host, const double *scale_host,
+                              const int32_t *even_host, int32_t n_basis, double gain, double readnoise, double *gram_out,
+                              int32_t *status_out, int32_t *count_out, void *stream);
+int apgpu_subtract_apply_f32(const float *convolved, const float *other, int64_t height, int64_t width, const float *kernels,
+                             int32_t radius, int32_t kernel_degree, const double *bg_host, int32_t bg_degree, int32_t flags, float a0,
+                             float *diff_out, float *matched_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
